@@ -51,6 +51,20 @@ class ModelConfig:
     num_classes_dis: int = 1       # Java:70 numClassesDis (binary real/fake)
     base_width: int = 64           # conv channel multiplier (dcgan64/128)
     dtype: str = "bf16"            # compute dtype on GPU
+    dis_dropout: float = 0.0       # DROP probability of the DropoutLayers
+    #                                added inside D (0 = none; the layer's
+    #                                keep is 1 - dis_dropout)
+    dis_input_noise_std: float = 0.0  # stddev of Gaussian "instance"
+    #                                noise on D's input (0 = none)
+
+    def validate_regularisers(self) -> None:
+        if not 0.0 <= self.dis_dropout < 1.0:
+            raise ValueError(
+                f"model.dis_dropout must be in [0, 1), got {self.dis_dropout}")
+        if not self.dis_input_noise_std >= 0.0:
+            raise ValueError(
+                "model.dis_input_noise_std must be >= 0, got "
+                f"{self.dis_input_noise_std}")
 
 
 @dataclass

@@ -4,6 +4,8 @@ from .layers import (
     Conv2dLayer,
     ConvTranspose2dLayer,
     DenseLayer,
+    DropoutLayer,
+    GaussianNoiseLayer,
     MaxPool2dLayer,
     MergeVertex,
     OutputLayer,
@@ -28,6 +30,8 @@ __all__ = [
     "MergeVertex",
     "Upsampling2dLayer",
     "ActivationLayer",
+    "DropoutLayer",
+    "GaussianNoiseLayer",
     "OutputLayer",
     "FeedForwardToCnnPreProcessor",
     "CnnToFeedForwardPreProcessor",

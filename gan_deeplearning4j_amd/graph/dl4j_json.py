@@ -25,6 +25,8 @@ from __future__ import annotations
 
 from typing import Optional
 
+import torch
+
 from . import layers as L
 from .builder import ComputationGraph, GraphBuilder, InputType
 
@@ -34,6 +36,7 @@ _NS_P = "org.deeplearning4j.nn.conf.preprocessor."
 _NS_A = "org.nd4j.linalg.activations.impl."
 _NS_LOSS = "org.nd4j.linalg.lossfunctions.impl."
 _NS_U = "org.nd4j.linalg.learning.config."
+_NS_D = "org.deeplearning4j.nn.conf.dropout."
 
 _ACT_TO_DL4J = {
     "tanh": "ActivationTanH",
@@ -84,11 +87,34 @@ def _base_layer_fields(graph: ComputationGraph, name: str,
     }
 
 
+def _idropout_to_dl4j(layer) -> dict:
+    """IDropout object of a stochastic layer (DL4J's Dropout.p is the
+    RETAIN probability, i.e. our keep)."""
+    if isinstance(layer, L.DropoutLayer):
+        return {"@class": _NS_D + "Dropout", "p": layer.keep}
+    return {"@class": _NS_D + "GaussianNoise", "stddev": layer.stddev}
+
+
+def _idropout_from_dl4j(d: dict):
+    cls = _cls(d)
+    if cls == "Dropout":
+        return L.DropoutLayer(d.get("p", 0.5))
+    if cls == "GaussianNoise":
+        return L.GaussianNoiseLayer(d.get("stddev", 0.0))
+    raise TypeError(f"unknown DL4J IDropout class {cls!r}")
+
+
 def _layer_to_dl4j(graph: ComputationGraph, name: str,
-                   layer: L.BaseLayer) -> dict:
+                   layer: L.BaseLayer, idropout: Optional[dict] = None
+                   ) -> dict:
     t = type(layer).__name__
     lr = getattr(layer, "lr", None)
     base = _base_layer_fields(graph, name, lr)
+    base["idropout"] = idropout
+    if t in ("DropoutLayer", "GaussianNoiseLayer"):
+        base["idropout"] = _idropout_to_dl4j(layer)
+        return {"@class": _NS_L + "DropoutLayer", **base,
+                "activationFn": _act("identity")}
     if t == "DenseLayer":
         return {"@class": _NS_L + "DenseLayer", **base,
                 "activationFn": _act(layer.activation), "hasBias": True,
@@ -159,19 +185,44 @@ def to_dl4j_json(graph: ComputationGraph) -> dict:
     """ComputationGraphConfiguration-shaped dict (DL4J beta3 layout)."""
     vertices = {}
     vertex_inputs = {}
+    # stochastic vertices that came from a layer's own `idropout` field
+    # (per-layer .dropOut()) fold back into that layer
+    folded = {}
+    n_consumers: dict = {}
+    for srcs in graph._vertex_inputs.values():
+        for s in srcs:
+            n_consumers[s] = n_consumers.get(s, 0) + 1
     for name in graph.layer_names():
+        layer = graph.layers[name]
+        owner = getattr(layer, "folded_into", None)
+        if (owner is not None and owner in graph.layers
+                and graph._vertex_inputs[owner] == [name]
+                and n_consumers.get(name) == 1
+                and name not in graph.output_names
+                and owner not in graph.preprocessors):
+            folded[owner] = name
+    for name in graph.layer_names():
+        if name in folded.values():
+            continue
         layer = graph.layers[name]
         vertex_inputs[name] = list(graph._vertex_inputs[name])
         if isinstance(layer, L.MergeVertex):
             vertices[name] = {"@class": _NS_G + "MergeVertex"}
             continue
+        idropout = None
+        proc_owner = name
+        if name in folded:
+            drop = folded[name]
+            idropout = _idropout_to_dl4j(graph.layers[drop])
+            vertex_inputs[name] = list(graph._vertex_inputs[drop])
+            proc_owner = drop
         vertices[name] = {
             "@class": _NS_G + "LayerVertex",
             "layerConf": {
                 "cacheMode": "NONE",
                 "epochCount": 0,
                 "iterationCount": 0,
-                "layer": _layer_to_dl4j(graph, name, layer),
+                "layer": _layer_to_dl4j(graph, name, layer, idropout),
                 "maxNumLineSearchIterations": 5,
                 "miniBatch": True,
                 "minimize": True,
@@ -181,8 +232,8 @@ def to_dl4j_json(graph: ComputationGraph) -> dict:
                 "variables": [],
             },
             "preProcessor": _preproc_to_dl4j(
-                graph.preprocessors[name]
-                if name in graph.preprocessors else None),
+                graph.preprocessors[proc_owner]
+                if proc_owner in graph.preprocessors else None),
         }
     input_types = []
     for n in graph.input_names:
@@ -267,6 +318,11 @@ def _layer_from_dl4j(ld: dict):
         return L.Upsampling2dLayer(sz[0] if isinstance(sz, list) else sz)
     if cls == "ActivationLayer":
         return L.ActivationLayer(act)
+    if cls == "DropoutLayer":
+        idrop = ld.get("idropout")
+        if not idrop:  # DL4J: a DropoutLayer without IDropout is identity
+            return L.DropoutLayer(1.0)
+        return _idropout_from_dl4j(idrop)
     raise TypeError(f"unknown DL4J layer class {cls!r}")
 
 
@@ -344,8 +400,18 @@ def from_dl4j_json(conf: dict, seed: int = 666,
             if _cls(v) == "MergeVertex":
                 gb.add_layer(name, L.MergeVertex(), *srcs)
             else:
-                layer = _layer_from_dl4j(v["layerConf"]["layer"])
+                ld = v["layerConf"]["layer"]
+                layer = _layer_from_dl4j(ld)
                 proc = _preproc_from_dl4j(v.get("preProcessor"))
+                idrop = ld.get("idropout")
+                if idrop and _cls(ld) != "DropoutLayer":
+                    # per-layer .dropOut(): acts on this layer's input,
+                    # after its preprocessor -> explicit vertex in front
+                    drop = _idropout_from_dl4j(idrop)
+                    drop.folded_into = name
+                    dname = name + "__idropout"
+                    gb.add_layer(dname, drop, *srcs, preprocessor=proc)
+                    srcs, proc = [dname], None
                 gb.add_layer(name, layer, *srcs, preprocessor=proc)
             placed.add(name)
             progressed = True
@@ -353,4 +419,12 @@ def from_dl4j_json(conf: dict, seed: int = 666,
             raise ValueError(f"cyclic or dangling vertexInputs: "
                              f"{sorted(pending)}")
     gb.set_outputs(*conf["networkOutputs"])
-    return gb.build()
+    graph = gb.build()
+    # the configuration carries no per-layer stream seed: derive distinct,
+    # reproducible ones from the graph seed (what init() would draw first)
+    gen = torch.Generator().manual_seed(graph.seed)
+    for name in graph.layer_names():
+        layer = graph.layers[name]
+        if isinstance(layer, (L.DropoutLayer, L.GaussianNoiseLayer)):
+            layer.reset_parameters(gen)
+    return graph

@@ -278,6 +278,85 @@ class ActivationLayer(BaseLayer):
         return OF.activation(x, self.activation, self.slope)
 
 
+class _StochasticLayer(BaseLayer):
+    """Shared plumbing of the stochastic layers (DL4J IDropout family).
+
+    The random state int64 [seed, calls] is a PLAIN tensor attribute —
+    neither parameter nor buffer: n_params()/summary() count buffers, and
+    GanTrainer.resume copies buffers positionally from a freshly restored
+    graph, which would silently reset the counter. It is mutated in place
+    only (a captured step keeps reading the same storage); `_apply` moves
+    it with the module. The seed is drawn from the graph's generator in
+    reset_parameters, so layers of one graph get different streams and the
+    same GraphBuilder seed reproduces them; `calls` starts at 0."""
+
+    def __init__(self):
+        super().__init__()
+        self.rng_state = OF.new_rng_state(0)
+        # set by the DL4J parser when this vertex came from a per-layer
+        # `.dropOut()` (idropout field) of the named layer; the emitter
+        # folds it back into that layer
+        self.folded_into: Optional[str] = None
+
+    def reset_parameters(self, gen: torch.Generator):
+        seed = int(torch.randint(0, 2 ** 62, (1,), generator=gen,
+                                 dtype=torch.int64))
+        self.rng_state[0] = seed
+        self.rng_state[1] = 0
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        moved = fn(self.rng_state)
+        if moved.dtype != torch.int64:  # .to(dtype)/.half(): state stays int64
+            moved = moved.to(torch.int64)
+        self.rng_state = moved
+        return self
+
+    @property
+    def seed(self) -> int:
+        return int(self.rng_state[0])
+
+    def set_seed(self, seed: int) -> None:
+        self.rng_state[0] = int(seed)
+
+    @property
+    def calls(self) -> int:
+        return int(self.rng_state[1])
+
+    def set_calls(self, calls: int) -> None:
+        self.rng_state[1] = int(calls)
+
+
+class DropoutLayer(_StochasticLayer):
+    """Inverted dropout (DL4J DropoutLayer / Dropout(p)); `keep` is the
+    retain probability, as DL4J's p. Identity unless self.training."""
+
+    def __init__(self, keep: float = 0.5):
+        super().__init__()
+        if not 0.0 < keep <= 1.0:
+            raise ValueError(f"DropoutLayer keep must be in (0, 1], got {keep}")
+        self.keep = float(keep)
+
+    def forward(self, x):
+        return OF.dropout(x, self.rng_state, self.keep, self.training)
+
+
+class GaussianNoiseLayer(_StochasticLayer):
+    """Additive N(0, stddev^2) noise (DL4J GaussianNoise); identity
+    gradient. Identity unless self.training."""
+
+    def __init__(self, stddev: float = 0.1):
+        super().__init__()
+        if stddev < 0.0:
+            raise ValueError(
+                f"GaussianNoiseLayer stddev must be >= 0, got {stddev}")
+        self.stddev = float(stddev)
+
+    def forward(self, x):
+        return OF.gaussian_noise(x, self.rng_state, self.stddev,
+                                 self.training)
+
+
 class FeedForwardToCnnPreProcessor(BaseLayer):
     """[N, H*W*C] -> [N, C, H, W] (reference Java:200).
 

@@ -48,11 +48,24 @@ _LAYER_FIELDS = {
     "MaxPool2dLayer": ("kernel", "stride"),
     "Upsampling2dLayer": ("scale",),
     "ActivationLayer": ("activation", "slope"),
+    "DropoutLayer": ("keep", "folded_into", "seed"),
+    "GaussianNoiseLayer": ("stddev", "folded_into", "seed"),
     "FeedForwardToCnnPreProcessor": ("height", "width", "channels", "channels_last"),
     "CnnToFeedForwardPreProcessor": ("channels_last",),
     "ReshapeVertex": ("shape",),
     "MergeVertex": (),
 }
+
+
+def _folded(layer, d: dict):
+    """Stochastic-layer settings beyond the ctor: the DL4J fold marker and
+    the stream seed (a restored graph is not re-initialised, so the seed
+    travels with the configuration; the call counter is trainer state)."""
+    layer.folded_into = d.get("folded_into")
+    if d.get("seed") is not None:
+        layer.set_seed(d["seed"])
+    return layer
+
 
 _CTOR_ARGS = {
     "DenseLayer": lambda d: L.DenseLayer(d["n_in"], d["n_out"], d["activation"],
@@ -77,6 +90,9 @@ _CTOR_ARGS = {
     "Upsampling2dLayer": lambda d: L.Upsampling2dLayer(d["scale"]),
     "ActivationLayer": lambda d: L.ActivationLayer(d["activation"],
                                                    d.get("slope", 0.2)),
+    "DropoutLayer": lambda d: _folded(L.DropoutLayer(d["keep"]), d),
+    "GaussianNoiseLayer": lambda d: _folded(
+        L.GaussianNoiseLayer(d["stddev"]), d),
     "FeedForwardToCnnPreProcessor": lambda d: L.FeedForwardToCnnPreProcessor(
         d["height"], d["width"], d["channels"],
         d.get("channels_last", False)),

@@ -20,7 +20,9 @@ from ..graph import (
     Conv2dLayer,
     ConvTranspose2dLayer,
     DenseLayer,
+    DropoutLayer,
     FeedForwardToCnnPreProcessor,
+    GaussianNoiseLayer,
     GraphBuilder,
     InputType,
     OutputLayer,
@@ -58,14 +60,24 @@ def _gen_graph(cfg: GanConfig, stages: list[int], s0: int) -> ComputationGraph:
 
 
 def _dis_graph(cfg: GanConfig, stages: list[int], s_last: int) -> ComputationGraph:
-    """image -> [Conv s2 lrelu (BN)] ... -> dense -> 1 logit (XENT)."""
+    """image -> [Conv s2 lrelu (BN)] ... -> dense -> 1 logit (XENT).
+
+    model.dis_dropout > 0 adds a DropoutLayer after every conv stage and
+    after d_dense_feat; model.dis_input_noise_std > 0 adds Gaussian noise
+    on the input. Both default to 0, which adds no vertex."""
     m = cfg.model
+    m.validate_regularisers()
+    keep = 1.0 - m.dis_dropout
     lr = cfg.optim.dis_learning_rate
     gb = GraphBuilder(seed=cfg.train.seed, optim_cfg=cfg.optim)
     gb.add_inputs("d_input")
     gb.set_input_types(InputType.convolutional(m.image_height, m.image_width,
                                                m.image_channels))
     prev = "d_input"
+    if m.dis_input_noise_std > 0:
+        gb.add_layer("d_noise_in", GaussianNoiseLayer(m.dis_input_noise_std),
+                     prev)
+        prev = "d_noise_in"
     c_prev = m.image_channels
     for i, c in enumerate(stages):
         name = f"d_conv_{i}"
@@ -76,12 +88,19 @@ def _dis_graph(cfg: GanConfig, stages: list[int], s_last: int) -> ComputationGra
             prev = f"d_bn_{i}"
         else:
             prev = name
+        if m.dis_dropout > 0:
+            gb.add_layer(f"d_drop_{i}", DropoutLayer(keep), prev)
+            prev = f"d_drop_{i}"
         c_prev = c
     gb.add_layer("d_dense_feat", DenseLayer(c_prev * s_last * s_last, 1024,
                                             activation="lrelu", lr=lr), prev,
                  preprocessor=CnnToFeedForwardPreProcessor(channels_last=True))
+    prev = "d_dense_feat"
+    if m.dis_dropout > 0:
+        gb.add_layer("d_drop_feat", DropoutLayer(keep), prev)
+        prev = "d_drop_feat"
     gb.add_layer("d_out", OutputLayer(1024, 1, activation="sigmoid",
-                                      loss="xent", lr=lr), "d_dense_feat")
+                                      loss="xent", lr=lr), prev)
     gb.set_outputs("d_out")
     return gb.build().init()
 

@@ -11,6 +11,8 @@ from ..graph import (
     BatchNormLayer,
     ComputationGraph,
     DenseLayer,
+    DropoutLayer,
+    GaussianNoiseLayer,
     GraphBuilder,
     InputType,
     OutputLayer,
@@ -38,11 +40,26 @@ def build_mlp_gan(cfg: GanConfig, hidden: int = 256
     db = GraphBuilder(seed=cfg.train.seed, optim_cfg=cfg.optim)
     db.add_inputs("d_input")
     db.set_input_types(InputType.feed_forward(f))
-    db.add_layer("d_dense_1", DenseLayer(f, hidden, "lrelu", dlr), "d_input")
+    # optional in-D regularisers (both default off: no extra vertex)
+    cfg.model.validate_regularisers()
+    drop, noise = cfg.model.dis_dropout, cfg.model.dis_input_noise_std
+    prev = "d_input"
+    if noise > 0:
+        db.add_layer("d_noise_in", GaussianNoiseLayer(noise), prev)
+        prev = "d_noise_in"
+    db.add_layer("d_dense_1", DenseLayer(f, hidden, "lrelu", dlr), prev)
+    prev = "d_dense_1"
+    if drop > 0:
+        db.add_layer("d_drop_1", DropoutLayer(1.0 - drop), prev)
+        prev = "d_drop_1"
     db.add_layer("d_dense_feat", DenseLayer(hidden, hidden, "lrelu", dlr),
-                 "d_dense_1")
+                 prev)
+    prev = "d_dense_feat"
+    if drop > 0:
+        db.add_layer("d_drop_feat", DropoutLayer(1.0 - drop), prev)
+        prev = "d_drop_feat"
     db.add_layer("d_out", OutputLayer(hidden, 1, "sigmoid", "xent", dlr),
-                 "d_dense_feat")
+                 prev)
     db.set_outputs("d_out")
     dis = db.build().init()
     return gen, dis

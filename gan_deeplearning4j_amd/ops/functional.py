@@ -151,6 +151,108 @@ def activation(x: torch.Tensor, act: str, slope: float = 0.2) -> torch.Tensor:
     return _apply_act(x, act, slope)
 
 
+def new_rng_state(seed: int = 0, device=None) -> torch.Tensor:
+    """Per-layer random state int64[2] = [seed, calls] (ops/philox_ref.py).
+    It lives on the layer's device so a captured step reads and advances
+    it there; it is only ever mutated in place."""
+    return torch.tensor([int(seed), 0], dtype=torch.int64, device=device)
+
+
+def _storage_order(x: torch.Tensor):
+    """Permutation that sorts x's dims by decreasing stride, or None when
+    x is not a dense permutation of a contiguous block."""
+    dims = sorted(range(x.dim()), key=lambda d: (-x.stride(d), d))
+    expect = 1
+    for d in reversed(dims):
+        if x.shape[d] != 1 and x.stride(d) != expect:
+            return None
+        expect *= x.shape[d]
+    return dims
+
+
+def _storage_flat_like(vals: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """Lay a flat storage-order vector out with x's shape and strides."""
+    dims = _storage_order(x)
+    if dims is None:
+        return vals.reshape(x.shape)
+    inv = [0] * len(dims)
+    for pos, d in enumerate(dims):
+        inv[d] = pos
+    return vals.reshape([x.shape[d] for d in dims]).permute(inv)
+
+
+class _DropoutRef(torch.autograd.Function):
+    """x * mask / keep with the multiply done in fp32 (the kernel's order
+    of operations), gradient dy * mask / keep."""
+
+    @staticmethod
+    def _masked_scale(t, mask, keep):
+        wide = torch.float64 if t.dtype == torch.float64 else torch.float32
+        scale = torch.tensor(1.0 / keep, dtype=wide)
+        out = torch.where(mask, t.to(wide) * scale,
+                          torch.zeros((), dtype=wide))
+        return out.to(t.dtype)
+
+    @staticmethod
+    def forward(ctx, x, mask, keep):
+        ctx.save_for_backward(mask)
+        ctx.keep = keep
+        return _DropoutRef._masked_scale(x, mask, keep)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (mask,) = ctx.saved_tensors
+        return _DropoutRef._masked_scale(dy, mask, ctx.keep), None, None
+
+
+def dropout(x: torch.Tensor, state: torch.Tensor, keep: float,
+            training: bool = True) -> torch.Tensor:
+    """Inverted dropout (DL4J Dropout(p): p = keep = retain probability).
+
+    state is the layer's int64 [seed, calls]; one training call consumes
+    the current `calls` value and advances it by 1 in place. Eval mode and
+    keep == 1 return x itself and leave the counter alone. CPU and GPU
+    draw the same Philox stream (ops/philox_ref.py)."""
+    if not 0.0 < keep <= 1.0:
+        raise ValueError(f"dropout keep must be in (0, 1], got {keep}")
+    if not training or keep == 1.0:
+        return x
+    if x.is_cuda:
+        from . import gpu_ops
+
+        return gpu_ops.dropout(x, state, keep)
+    from . import philox_ref
+
+    seed, calls = (int(v) for v in state.tolist())
+    m = philox_ref.dropout_keep_mask(x.numel(), seed, calls, keep)
+    mask = _storage_flat_like(torch.from_numpy(m), x)
+    state[1] += 1
+    return _DropoutRef.apply(x, mask, keep)
+
+
+def gaussian_noise(x: torch.Tensor, state: torch.Tensor, stddev: float,
+                   training: bool = True) -> torch.Tensor:
+    """y = x + stddev * N(0, 1) (DL4J GaussianNoise); identity gradient.
+    Same state/counter contract as dropout()."""
+    if stddev < 0.0:
+        raise ValueError(f"gaussian noise stddev must be >= 0, got {stddev}")
+    if not training or stddev == 0.0:
+        return x
+    if x.is_cuda:
+        from . import gpu_ops
+
+        return gpu_ops.gaussian_noise(x, state, stddev)
+    from . import philox_ref
+
+    seed, calls = (int(v) for v in state.tolist())
+    nz = philox_ref.gaussian_noise_ref(x.numel(), seed, calls)
+    noise = _storage_flat_like(torch.from_numpy(nz), x)
+    state[1] += 1
+    if x.dtype == torch.float64:
+        return x + stddev * noise
+    return (x.float() + stddev * noise.float()).to(x.dtype)
+
+
 def bce_with_logits_loss(
     logits: torch.Tensor, labels: torch.Tensor
 ) -> torch.Tensor:

@@ -999,6 +999,72 @@ def activation(x, act, slope=0.2):
     return _Act.apply(x, code, slope)
 
 
+# ========================================================= dropout / noise
+def _bf_dense(t: torch.Tensor) -> torch.Tensor:
+    """bf16 cast that keeps any dense stride order (channels-last views
+    pass through with zero copies; the kernels walk storage order). Only a
+    genuinely strided tensor (e.g. a channel-trimmed view) is copied, into
+    channels-last when that is its innermost axis."""
+    from .functional import _storage_order
+
+    t = t.to(torch.bfloat16)
+    if _storage_order(t) is not None:
+        return t
+    if t.dim() == 4 and t.stride(1) == 1:
+        return t.contiguous(memory_format=torch.channels_last)
+    return t.contiguous()
+
+
+class _Dropout(torch.autograd.Function):
+    """Inverted dropout on the Philox kernel. The kernel reads
+    [seed, calls] from `state` on the device; the counter is advanced by a
+    stream-ordered in-place add AFTER the launch (captured with the step,
+    like Updater._t_dev). Backward uses only the saved mask bytes."""
+
+    @staticmethod
+    def forward(ctx, x, state, keep: float):
+        xb = _bf_dense(x)
+        y, mask = hip_ext().dropout_fwd(xb, state, keep)
+        state[1:2].add_(1)
+        ctx.save_for_backward(mask)
+        ctx.keep = keep
+        ctx.x_dtype = x.dtype
+        ctx.strides = y.stride()
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (mask,) = ctx.saved_tensors
+        dyb = dy.to(torch.bfloat16)
+        if dyb.stride() != ctx.strides:
+            # the mask is in the forward's storage order
+            dyb = torch.empty_strided(dy.shape, ctx.strides, dtype=dyb.dtype,
+                                      device=dyb.device).copy_(dyb)
+        dx = hip_ext().dropout_bwd(dyb, mask, ctx.keep)
+        return dx.to(ctx.x_dtype), None, None
+
+
+class _GaussianNoise(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, state, stddev: float):
+        y = hip_ext().gaussian_noise_fwd(_bf_dense(x), state, stddev)
+        state[1:2].add_(1)
+        ctx.x_dtype = x.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy.to(ctx.x_dtype), None, None
+
+
+def dropout(x, state, keep):
+    return _Dropout.apply(x, state, keep)
+
+
+def gaussian_noise(x, state, stddev):
+    return _GaussianNoise.apply(x, state, stddev)
+
+
 # ==================================================================== losses
 class _BceWithLogits(torch.autograd.Function):
     @staticmethod

@@ -92,6 +92,14 @@ void launch_act_fwd(const void*, void*, long, int, float, hipStream_t);
 void launch_act_bwd(const void*, const void*, void*, long, int, float,
                     hipStream_t);
 void launch_col_sum(const void*, float*, long, int, hipStream_t);
+int dropout_grid_cap();
+int dropout_block_size();
+void launch_dropout_fwd(const void*, void*, void*, const void*, long,
+                        unsigned int, float, hipStream_t);
+void launch_dropout_bwd(const void*, const void*, void*, long, float,
+                        hipStream_t);
+void launch_gaussian_noise_fwd(const void*, void*, const void*, long, float,
+                               hipStream_t);
 void launch_bce_fwd(const void*, const void*, float*, long, hipStream_t);
 void launch_bce_bwd(const void*, const void*, void*, float, long, hipStream_t);
 void launch_softmax_xent_fwd(const void*, const void*, float*, void*, int,
@@ -654,6 +662,71 @@ torch::Tensor act_bwd(torch::Tensor dy, torch::Tensor y, int64_t act,
   return dx;
 }
 
+// ------------------------------------------------------ dropout / noise
+// Data tensors may be any dense permutation (channels-last views pass with
+// zero copies): the kernels walk STORAGE order and empty_like keeps strides.
+void check_bf16_dense(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
+  TORCH_CHECK(t.is_non_overlapping_and_dense(), name,
+              " must be non-overlapping and dense");
+}
+
+void check_rng_state(const torch::Tensor& state, const torch::Tensor& x) {
+  TORCH_CHECK(state.is_cuda() && state.device() == x.device(),
+              "state must be on the same device as x");
+  TORCH_CHECK(state.scalar_type() == torch::kInt64 && state.numel() == 2 &&
+                  state.is_contiguous(),
+              "state must be an int64 tensor of 2 elements [seed, calls]");
+}
+
+std::vector<torch::Tensor> dropout_fwd(torch::Tensor x, torch::Tensor state,
+                                       double keep) {
+  check_bf16_dense(x, "x");
+  check_rng_state(state, x);
+  TORCH_CHECK(keep > 0.0 && keep <= 1.0, "dropout needs 0 < keep <= 1, got ",
+              keep);
+  int64_t n = x.numel();
+  torch::Tensor y = torch::empty_like(x);
+  torch::Tensor mask =
+      torch::empty({(n + 7) / 8}, x.options().dtype(torch::kUInt8));
+  unsigned int thresh = (unsigned int)std::llround(keep * 65536.0);
+  if (n > 0)
+    launch_dropout_fwd(x.data_ptr(), y.data_ptr(), mask.data_ptr(),
+                       state.data_ptr(), (long)n, thresh,
+                       (float)(1.0 / keep), cur_stream());
+  return {y, mask};
+}
+
+torch::Tensor dropout_bwd(torch::Tensor dy, torch::Tensor mask, double keep) {
+  check_bf16_dense(dy, "dy");
+  TORCH_CHECK(keep > 0.0 && keep <= 1.0, "dropout needs 0 < keep <= 1, got ",
+              keep);
+  int64_t n = dy.numel();
+  TORCH_CHECK(mask.is_cuda() && mask.device() == dy.device() &&
+                  mask.scalar_type() == torch::kUInt8 &&
+                  mask.is_contiguous() && mask.numel() == (n + 7) / 8,
+              "mask must be uint8[ceil(n/8)] on dy's device");
+  torch::Tensor dx = torch::empty_like(dy);
+  if (n > 0)
+    launch_dropout_bwd(dy.data_ptr(), mask.data_ptr(), dx.data_ptr(),
+                       (long)n, (float)(1.0 / keep), cur_stream());
+  return dx;
+}
+
+torch::Tensor gaussian_noise_fwd(torch::Tensor x, torch::Tensor state,
+                                 double stddev) {
+  check_bf16_dense(x, "x");
+  check_rng_state(state, x);
+  TORCH_CHECK(stddev >= 0.0, "gaussian noise needs stddev >= 0, got ",
+              stddev);
+  torch::Tensor y = torch::empty_like(x);
+  if (x.numel() > 0)
+    launch_gaussian_noise_fwd(x.data_ptr(), y.data_ptr(), state.data_ptr(),
+                              (long)x.numel(), (float)stddev, cur_stream());
+  return y;
+}
+
 torch::Tensor col_sum(torch::Tensor a) {
   check_bf16(a, "a");
   int64_t m = a.size(0), n = a.size(1);
@@ -1078,6 +1151,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("act_bwd", &act_bwd);
   mod.def("act_bwd_bias", &act_bwd_bias,
           "fused activation backward + bias gradient");
+  mod.def("dropout_fwd", &dropout_fwd,
+          "inverted dropout: (y, mask bytes); Philox state read on device");
+  mod.def("dropout_bwd", &dropout_bwd, "dx = dy * mask / keep");
+  mod.def("gaussian_noise_fwd", &gaussian_noise_fwd,
+          "y = x + stddev * N(0,1); Philox state read on device");
+  mod.attr("DROPOUT_GRID_CAP") = dropout_grid_cap();
+  mod.attr("DROPOUT_BLOCK") = dropout_block_size();
   mod.def("col_sum", &col_sum);
   mod.def("bce_fwd", &bce_fwd);
   mod.def("bce_bwd", &bce_bwd);

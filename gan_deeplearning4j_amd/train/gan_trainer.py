@@ -71,6 +71,8 @@ class GanTrainer:
         capture: bool = False,
     ):
         self.cfg = cfg
+        # in-D regulariser knobs: 0 <= dis_dropout < 1, noise std >= 0
+        cfg.model.validate_regularisers()
         self.device = device or torch.device(
             "cuda" if torch.cuda.is_available() and cfg.train.use_gpu else "cpu"
         )
@@ -356,6 +358,16 @@ class GanTrainer:
         log.info("training step captured as hipGraph")
 
     # ------------------------------------------------- save / resume
+    def _stochastic_layers(self):
+        """(key, layer) of every Dropout/GaussianNoise vertex of G and D."""
+        from ..graph.layers import DropoutLayer, GaussianNoiseLayer
+
+        for gname, graph in (("gen", self.gen), ("dis", self.dis)):
+            for lname in graph.layer_names():
+                layer = graph.layers[lname]
+                if isinstance(layer, (DropoutLayer, GaussianNoiseLayer)):
+                    yield f"{gname}/{lname}", layer
+
     def save(self, out_dir) -> None:
         """Checkpoint both graphs (DL4J zip layout + updater state),
         the EMA state and the step counter. The reference protocol
@@ -370,6 +382,11 @@ class GanTrainer:
         state = {"it": self.it}
         if self._ema is not None:
             state["ema"] = [e.cpu() for e in self._ema]
+        # call counters of the stochastic layers, read back from the
+        # device (replays advance them there), like Updater's t
+        rng = {key: layer.calls for key, layer in self._stochastic_layers()}
+        if rng:
+            state["rng"] = rng
         torch.save(state, out / "trainer_state.pt")
 
     def resume(self, out_dir) -> bool:
@@ -398,6 +415,12 @@ class GanTrainer:
             with torch.no_grad():
                 for e, s in zip(self._ema, state["ema"]):
                     e.copy_(s.to(e.device))
+        # after the positional buffer copy, and in place: a captured step
+        # keeps reading the same state storage
+        rng = state.get("rng", {})
+        for key, layer in self._stochastic_layers():
+            if key in rng:
+                layer.set_calls(rng[key])
         return True
 
     @contextmanager
