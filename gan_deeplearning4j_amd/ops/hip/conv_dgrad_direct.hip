@@ -23,9 +23,17 @@
 // Tile: BM class-pixels x 64 c (BM 128 or 64), 4 waves; LDS = dy
 // region + 32 KiB W double-buffer (ctile reuses the W area).
 // Eligibility (launcher): stride == 2, Wc | BM, (Hc*Wc) % BM == 0,
-// C8 % 64 == 0, Ko8 % 128 == 0 == ldw, region + 32 KiB <= 120 KiB.
+// C8 % 64 == 0, Ko8 % 128 == 0 == ldw, region + 32 KiB <= 80 KiB
+// (two blocks per CU).
 // Covers conv2/conv3-class dgrads of the DCGAN family; everything
 // else falls back to dcol+col2im (gemm.hip / im2col.hip).
+//
+// conv_dgrad_direct_p (below) is the persistent class-fused variant of
+// the same arithmetic; the launchers try it first and keep this kernel
+// as the fallback and A/B arm (GDLJ_DGRAD_PERSIST=0).
+
+#include <algorithm>
+#include <cstdlib>
 
 #include "common.h"
 
@@ -318,7 +326,525 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct(
   }
 }
 
+// ---------------------------------------------------------------------
+// Persistent class-fused variant.
+//
+// A block walks a strided sequence of tiles (grid = CUs x 2, no
+// inter-block communication).  A tile is one BM class-pixel tile times
+// ALL of C8 and either all four parity classes or, where the full
+// union region does not fit two blocks per CU, the two classes of one
+// row parity (qsplit).  The union dy region of the tile's classes is
+// staged ONCE and every class / 64-channel c-tile runs its tap set out
+// of it, so the region is no longer re-staged per class and per c-tile.
+//
+// The W slices form one stream across classes, c-tiles and tiles: the
+// slice after the last one of a (class, c-tile) is already in flight
+// while the epilogue runs, and the epilogue's ctile is the W buffer the
+// last slice just released (the prefetch targets the other one), so the
+// double buffer never drains.  The next tile's region is issued right
+// after the tile's last MFMA slice, under the last epilogue.
+//
+// Bias / BN-statistics partials stay in registers across all tiles and
+// go through the LDS tree + atomics once per block.  Per output element
+// the accumulation sequence (taps, 128-co chunk, kc) and the epilogue
+// expressions are those of conv_dgrad_direct, so dx / y are
+// bit-identical; only the order of the fp32 partial sums differs.
+namespace cdd {
+// per-axis parity-class geometry: first tap, tap count, dy offset of
+// tap 0 (class pixel h reads dy rows h + boff - k, k < ntap)
+DEV_INLINE int p_tap0(int q, int pad) { return (q + pad) & 1; }
+DEV_INLINE int p_ntap(int q, int pad, int R) {
+  return (R - p_tap0(q, pad) + 1) >> 1;
+}
+DEV_INLINE int p_boff(int q, int pad) {
+  return (q + pad - p_tap0(q, pad)) >> 1;
+}
+// Workgroup barrier for LDS traffic only.  __syncthreads() carries a
+// release fence that drains vmcnt to 0, i.e. waits for the prefetched
+// W slice / region at every barrier and serializes the pipeline
+// (same finding as gemm8p.hip).  This one completes the wave's own LDS
+// reads/writes and leaves the LDS-DMA loads in flight; their arrival
+// is guarded by the counted vmcnt waits.
+DEV_INLINE void p_lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+}  // namespace cdd
+
+// PACT = y0 given (producer act-backward epilogue).
+template <int MI, int NCT, bool PACT>
+__global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
+    const unsigned short* __restrict__ dy,   // [N][Ho][Wo][Ko8]
+    const unsigned short* __restrict__ Wt,   // [R*S*C8][ldw], k = co
+    unsigned short* __restrict__ dx,         // [N][H][W][C8]
+    const unsigned short* __restrict__ y0,   // producer act out (or null)
+    float* __restrict__ part,                // [2048][C8] f32 (or null)
+    const float* __restrict__ bias_fwd,      // convT fwd bias (or null)
+    float* __restrict__ stats_part,          // [2048][2*C8] f32 (or null)
+    const unsigned short* __restrict__ zp,   // 16B zero page
+    int H, int W, int C8, int Ho, int Wo, int Ko8, long ldw,
+    int R, int S, int pad, int act, float slope,
+    int Hc, int Wc, int rgn_rows, int rgn_cols, FastDiv fWc,
+    int ntiles, int qsplit) {
+  using namespace cdd;
+  constexpr int BM = MI * 64;
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  char* rgn = lds;                                  // union dy region
+  const int rgn_b = rgn_rows * rgn_cols * Ko8 * 2;
+  auto wbuf = [&](int i) -> char* { return lds + rgn_b + i * WSLICE_B; };
+
+  const int rows_c = BM / Wc;
+  const int tpi = (Hc * Wc) / BM;          // pixel tiles per image
+  const int co_chunks = Ko8 >> 3;          // power of two (launcher)
+  const int cmask = co_chunks - 1;
+  const int csh = 31 - __builtin_clz(co_chunks);
+  const int ncell = rgn_rows * rgn_cols * co_chunks;
+  const int nj = Ko8 >> 7;                 // 128-co chunks per tap
+
+  // union column window over both column parities
+  const int lo_w = min(p_boff(0, pad) - (p_ntap(0, pad, S) - 1),
+                       p_boff(1, pad) - (p_ntap(1, pad, S) - 1));
+  // union row window: both row parities, or the tile's own one (qsplit)
+  auto row_lo = [&](int tile) {
+    int a = p_boff(0, pad) - (p_ntap(0, pad, R) - 1);
+    int b = p_boff(1, pad) - (p_ntap(1, pad, R) - 1);
+    return qsplit ? ((tile & 1) ? b : a) : min(a, b);
+  };
+
+  // ---- stage a tile's region: [rgn_rows][rgn_cols][Ko8], zero halo,
+  // source-side chunk swizzle slot = j ^ (cc & cmask) as above ----
+  auto stage_region = [&](int tile) {
+    int pt = qsplit ? (tile >> 1) : tile;
+    int n = pt / tpi;
+    int hc0 = (pt - n * tpi) * rows_c;
+    int h0 = hc0 + row_lo(tile);
+    for (int cell = threadIdx.x; cell < ncell; cell += 256) {
+      int rc_ = cell >> csh;
+      int slot = cell & cmask;
+      int rr = rc_ / rgn_cols;
+      int cc = rc_ - rr * rgn_cols;
+      int j = slot ^ (cc & cmask);
+      int hig = h0 + rr;
+      int wig = lo_w + cc;
+      const unsigned short* src = zp;
+      if (hig >= 0 && hig < Ho && wig >= 0 && wig < Wo)
+        src = dy + (((long)n * Ho + hig) * Wo + wig) * Ko8 + j * 8;
+      char* dst = rgn + (cell & ~63) * 16;
+      GLDS16(src, dst);
+    }
+  };
+
+  // W source of slice sl of (class cls, c-tile ct)
+  auto wsrc_for = [&](int cls, int ct, int sl) {
+    int qh = cls >> 1, qw = cls & 1;
+    int r0 = p_tap0(qh, pad), s0 = p_tap0(qw, pad);
+    int Sc = p_ntap(qw, pad, S);
+    int tapj = sl / nj, j = sl - tapj * nj;
+    int rc_ = tapj / Sc, sc_ = tapj - rc_ * Sc;
+    int tap = (r0 + 2 * rc_) * S + (s0 + 2 * sc_);
+    return Wt + ((long)tap * C8 + ct * 64) * ldw + j * 128;
+  };
+
+  const int wid = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int fr = lane & 15, fq = lane >> 4;
+
+  // this lane's A-side class pixels: px_l = wid*(MI*16) + mi*16 + fr
+  int pxh[MI], pxw[MI];
+  #pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    int pxl = wid * (MI * 16) + mi * 16 + fr;
+    int hl = (int)fdiv((unsigned)pxl, fWc);
+    pxh[mi] = hl;
+    pxw[mi] = pxl - hl * Wc;
+  }
+
+  const int t2 = threadIdx.x;
+  const int seg = t2 & 7;            // fixed c-block per thread
+  float bsum[NCT][8], ssum[NCT][8], ssq[NCT][8];
+  #pragma unroll
+  for (int k = 0; k < NCT; ++k)
+    #pragma unroll
+    for (int jj = 0; jj < 8; ++jj)
+      bsum[k][jj] = ssum[k][jj] = ssq[k][jj] = 0.f;
+
+  // convT-forward bias of this lane's columns, loaded once: a global
+  // load inside the epilogue would make the compiler drain the
+  // in-flight prefetches to get at its value
+  float biasv[NCT][4];
+  #pragma unroll
+  for (int k = 0; k < NCT; ++k)
+    #pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      biasv[k][ni] =
+          bias_fwd != nullptr ? bias_fwd[k * 64 + ni * 16 + fr] : 0.f;
+      // consume the value here, ahead of every LDS-DMA load, so its
+      // wait is placed now and not at the uses inside the tile loop
+      asm volatile("" : "+v"(biasv[k][ni]));
+    }
+
+  // prologue: first region + first W slice; the first in-loop wait
+  // covers both (loads complete in issue order)
+  int tile = blockIdx.x;
+  const int cls0 = qsplit ? (tile & 1) * 2 : 0;
+  stage_region(tile);
+  cdd_stage_w64(wsrc_for(cls0, 0, 0), ldw, 0, wbuf(0));
+  cdd_stage_w64(wsrc_for(cls0, 0, 0), ldw, 64, wbuf(0) + 8 * 1024);
+
+  int g = 0;                         // running slice count -> W buffer
+  for (; tile < ntiles; tile += gridDim.x) {
+    const int pt = qsplit ? (tile >> 1) : tile;
+    const int n = pt / tpi;
+    const int hc0 = (pt - n * tpi) * rows_c;
+    const int cb = qsplit ? (tile & 1) * 2 : 0;
+    const int ce = qsplit ? cb + 2 : 4;
+    const int ntile = tile + (int)gridDim.x;
+    const bool has_next = ntile < ntiles;
+    const int lo_h = row_lo(tile);
+
+    for (int cls = cb; cls < ce; ++cls) {
+      const int qh = cls >> 1, qw = cls & 1;
+      const int Rc = p_ntap(qh, pad, R), Sc = p_ntap(qw, pad, S);
+      const int rb0 = p_boff(qh, pad), wb0 = p_boff(qw, pad);
+      const int nslice = Rc * Sc * nj;
+
+      for (int ct = 0; ct < NCT; ++ct) {
+        const bool last_ct = (cls + 1 == ce) && (ct + 1 == NCT);
+        f32x4 acc[MI][4];
+        #pragma unroll
+        for (int i = 0; i < MI; ++i)
+          #pragma unroll
+          for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+
+        for (int sl = 0; sl < nslice; ++sl, ++g) {
+          int tapj = sl / nj;
+          int j = sl - tapj * nj;
+          int rc_ = tapj / Sc, sc_ = tapj - rc_ * Sc;
+          int cur = g & 1;
+          // next slice of the stream: this (class, c-tile), else the
+          // next c-tile, class or tile
+          const unsigned short* ws = nullptr;
+          if (sl + 1 < nslice) ws = wsrc_for(cls, ct, sl + 1);
+          else if (ct + 1 < NCT) ws = wsrc_for(cls, ct + 1, 0);
+          else if (cls + 1 < ce) ws = wsrc_for(cls + 1, 0, 0);
+          else if (has_next)
+            ws = wsrc_for(qsplit ? (ntile & 1) * 2 : 0, 0, 0);
+          if (ws != nullptr) {
+            cdd_stage_w64(ws, ldw, 0, wbuf(cur ^ 1));
+            cdd_stage_w64(ws, ldw, 64, wbuf(cur ^ 1) + 8 * 1024);
+            // Loads and stores retire in issue order.  Right after an
+            // epilogue the newest operations are its BM/32 dx stores
+            // and the 4 loads just issued; this slice's W and the
+            // region are older, so the stores may stay outstanding.
+            if (sl == 0 && g > 0)
+              asm volatile("s_waitcnt vmcnt(%0)" ::"i"(4 + BM / 32)
+                           : "memory");
+            else
+              asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+          } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          }
+          p_lds_barrier();
+          // region coordinates for this tap (always in-grid; halo
+          // cells are zero)
+          long abase[MI];
+          int axor[MI];
+          #pragma unroll
+          for (int mi = 0; mi < MI; ++mi) {
+            int rr = pxh[mi] + rb0 - rc_ - lo_h;
+            int cc = pxw[mi] + wb0 - sc_ - lo_w;
+            abase[mi] = ((long)rr * rgn_cols + cc) * Ko8 * 2;
+            axor[mi] = cc & cmask;
+          }
+          const char* Wl = wbuf(cur);
+          #pragma unroll
+          for (int kc = 0; kc < 4; ++kc) {
+            int jc = j * 16 + kc * 4 + fq;   // 16B co-chunk within Ko8
+            bf16x8 a[MI], b[4];
+            #pragma unroll
+            for (int mi = 0; mi < MI; ++mi)
+              a[mi] = *(const bf16x8*)(rgn + abase[mi] +
+                                       ((jc ^ axor[mi]) << 4));
+            int sub = kc >> 1, kslot = (kc & 1) * 4 + fq;
+            #pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+              b[ni] = cdd_wfrag(Wl + sub * 8 * 1024, ni * 16 + fr, kslot);
+            #pragma unroll
+            for (int mi = 0; mi < MI; ++mi)
+              #pragma unroll
+              for (int ni = 0; ni < 4; ++ni)
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+          }
+          p_lds_barrier();  // all waves done with wbuf(cur) + region
+        }
+
+        // the tile's last MFMA slice is done: the region is dead, put
+        // the next tile's region in flight under this epilogue
+        if (last_ct && has_next) stage_region(ntile);
+        // keep the region loads ahead of the epilogue's stores (the
+        // counted wait above relies on that order)
+        asm volatile("" ::: "memory");
+
+        // output addresses of this thread's pieces; the producer's
+        // activation output is fetched now so that its latency runs
+        // under the ctile transpose
+        long eaddr[BM / 32];
+        s16x8 yin[BM / 32];
+        #pragma unroll
+        for (int i = 0; i < BM / 32; ++i) {
+          int row = (i * 256 + t2) >> 3;  // BM*8 pieces = BM rows x 8 segs
+          int hl = (int)fdiv((unsigned)row, fWc);
+          int wcl = row - hl * Wc;
+          int hi = qh + 2 * (hc0 + hl);
+          int wi = qw + 2 * wcl;
+          eaddr[i] = (((long)n * H + hi) * W + wi) * C8 + ct * 64 + seg * 8;
+        }
+        if constexpr (PACT) {
+          #pragma unroll
+          for (int i = 0; i < BM / 32; ++i)
+            yin[i] = *(const s16x8*)(y0 + eaddr[i]);
+        }
+
+        // ---- epilogue: ctile = the W buffer the last slice released
+        // (the in-flight prefetch targets the other one) ----
+        unsigned short* ctile = (unsigned short*)wbuf((g - 1) & 1);
+        #pragma unroll
+        for (int mi = 0; mi < MI; ++mi) {
+          #pragma unroll
+          for (int ni = 0; ni < 4; ++ni) {
+            int lc = ni * 16 + fr;
+            float bv = 0.f;
+            #pragma unroll
+            for (int k = 0; k < NCT; ++k)
+              if (ct == k) bv = biasv[k][ni];
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              int lr = wid * (MI * 16) + mi * 16 + fq * 4 + r;
+              float v = acc[mi][ni][r];
+              if (bias_fwd != nullptr) v = act_fwd(v + bv, act, slope);
+              ctile[lr * 64 + lc] = f2bf(v);
+            }
+          }
+        }
+        p_lds_barrier();
+        if constexpr (PACT) {
+          // take the wait for all fetched y0 pieces here, once; left to
+          // the uses below, each one also waits for the previous store
+          #pragma unroll
+          for (int i = 0; i < BM / 32; ++i)
+            asm volatile("" : "+v"(yin[i]));
+        }
+        #pragma unroll
+        for (int i = 0; i < BM / 32; ++i) {
+          int row = (i * 256 + t2) >> 3;
+          const long addr = eaddr[i];
+          s16x8 v = *(const s16x8*)(ctile + row * 64 + seg * 8);
+          if constexpr (PACT) {
+            const s16x8 yv = yin[i];
+            #pragma unroll
+            for (int jj = 0; jj < 8; ++jj) {
+              float d = bf2f((unsigned short)v[jj]) *
+                        act_bwd_from_y(bf2f((unsigned short)yv[jj]), act,
+                                       slope);
+              v[jj] = (short)f2bf(d);
+              #pragma unroll
+              for (int k = 0; k < NCT; ++k)
+                if (ct == k) bsum[k][jj] += d;
+            }
+          }
+          if (stats_part != nullptr) {
+            #pragma unroll
+            for (int jj = 0; jj < 8; ++jj) {
+              float yv = bf2f((unsigned short)v[jj]);
+              #pragma unroll
+              for (int k = 0; k < NCT; ++k)
+                if (ct == k) {
+                  ssum[k][jj] += yv;
+                  ssq[k][jj] += yv * yv;
+                }
+            }
+          }
+          *(s16x8*)(dx + addr) = v;
+        }
+        p_lds_barrier();  // ctile reads done before it is restaged as W
+      }
+    }
+  }
+
+  // ---- once per block: LDS tree + atomics over the register partials
+  // (region and W buffers are dead, nothing is in flight) ----
+  float* red = (float*)rgn;
+  const int rrow = t2 >> 3;  // 32 contributor rows per seg
+  auto reduce_and_add = [&](const float* vec, float* dst) {
+    #pragma unroll
+    for (int jj = 0; jj < 8; ++jj)
+      red[(rrow * 8 + seg) * 8 + jj] = vec[jj];
+    __syncthreads();
+    for (int off = 16; off > 0; off >>= 1) {
+      if (rrow < off) {
+        #pragma unroll
+        for (int jj = 0; jj < 8; ++jj)
+          red[(rrow * 8 + seg) * 8 + jj] +=
+              red[((rrow + off) * 8 + seg) * 8 + jj];
+      }
+      __syncthreads();
+    }
+    if (rrow == 0) {
+      #pragma unroll
+      for (int jj = 0; jj < 8; ++jj)
+        atomicAdd(&dst[seg * 8 + jj], red[seg * 8 + jj]);
+    }
+    __syncthreads();  // red is reused by the next reduction
+  };
+  #pragma unroll
+  for (int k = 0; k < NCT; ++k) {
+    if (PACT && part != nullptr)
+      reduce_and_add(bsum[k],
+                     part + (long)(blockIdx.x & 2047) * C8 + k * 64);
+    if (stats_part != nullptr) {
+      float* srow = stats_part + (long)(blockIdx.x & 2047) * 2 * C8;
+      reduce_and_add(ssum[k], srow + k * 64);
+      reduce_and_add(ssq[k], srow + C8 + k * 64);
+    }
+  }
+}
+
+// one-time dynamic-LDS opt-in for every instantiation of both kernels
+static void cdd_set_attrs_once() {
+  static int attr_done = 0;
+  if (attr_done) return;
+  const void* fns[] = {
+      reinterpret_cast<const void*>(&conv_dgrad_direct<2>),
+      reinterpret_cast<const void*>(&conv_dgrad_direct<1>),
+      reinterpret_cast<const void*>(&conv_dgrad_direct_p<2, 1, false>),
+      reinterpret_cast<const void*>(&conv_dgrad_direct_p<2, 2, false>),
+      reinterpret_cast<const void*>(&conv_dgrad_direct_p<1, 1, false>),
+      reinterpret_cast<const void*>(&conv_dgrad_direct_p<1, 2, false>),
+      reinterpret_cast<const void*>(&conv_dgrad_direct_p<2, 1, true>),
+      reinterpret_cast<const void*>(&conv_dgrad_direct_p<2, 2, true>),
+      reinterpret_cast<const void*>(&conv_dgrad_direct_p<1, 1, true>),
+      reinterpret_cast<const void*>(&conv_dgrad_direct_p<1, 2, true>),
+  };
+  for (const void* f : fns)
+    (void)hipFuncSetAttribute(
+        f, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
+  attr_done = 1;
+}
+
+namespace cdd {
+constexpr int PF_BM64 = 1 << 24;    // flag bits above the LDS byte count
+constexpr int PF_QSPLIT = 1 << 25;
+constexpr int PF_LDS_MASK = (1 << 24) - 1;
+
+// host mirror of the per-axis class geometry
+inline void p_axis_window(int pad, int R, int q, int* lo, int* hi) {
+  int t0 = (q + pad) & 1;
+  int nt = (R - t0 + 1) >> 1;
+  int bo = (q + pad - t0) >> 1;
+  *lo = bo - (nt - 1);
+  *hi = bo;
+}
+// region extent along one axis for `len` class pixels: the union of
+// both parities, or (qsplit) the larger single-parity window
+inline int p_axis_extent(int len, int pad, int R, bool qsplit) {
+  int l0, h0, l1, h1;
+  p_axis_window(pad, R, 0, &l0, &h0);
+  p_axis_window(pad, R, 1, &l1, &h1);
+  if (qsplit) return len + std::max(h0 - l0, h1 - l1);
+  return len + std::max(h0, h1) - std::min(l0, l1);
+}
+}  // namespace cdd
+
 extern "C" {
+
+// Persistent kernel eligibility: 0, or LDS bytes | PF_* flags.  On top
+// of the one-shot kernel's conditions: C8 <= 128 (register partials
+// per c-tile), Ko8 a power of two (shift/mask cell decode), and the
+// union region + 32 KiB W double buffer within 80 KiB (two blocks per
+// CU).  Full four-class fusion is preferred; where its region is too
+// large the tile is split by row parity (two classes per staging).
+int conv_dgrad_direct_p_eligible(int H, int W, int C8, int Ko8, long ldw,
+                                 int R, int S, int stride, int pad) {
+  using namespace cdd;
+  if (stride != 2 || (C8 != 64 && C8 != 128) || Ko8 % 128 != 0 ||
+      (Ko8 & (Ko8 - 1)) != 0 || ldw != Ko8)
+    return 0;
+  if (R < 2 || S < 2 || R > 8 || S > 8 || (H & 1) || (W & 1)) return 0;
+  if (pad < 0) return 0;
+  int Hc = H / 2, Wc = W / 2;
+  for (int bm : {128, 64}) {
+    if (Wc > bm || bm % Wc != 0 || (Hc * Wc) % bm != 0) continue;
+    int rows_c = bm / Wc;
+    for (int qsplit : {0, 1}) {
+      int rgn_rows = p_axis_extent(rows_c, pad, R, qsplit != 0);
+      int rgn_cols = p_axis_extent(Wc, pad, S, false);
+      int lds_b = rgn_rows * rgn_cols * Ko8 * 2 + WBUF_B;
+      if (lds_b > 80 * 1024) continue;
+      return lds_b | (bm == 64 ? PF_BM64 : 0) | (qsplit ? PF_QSPLIT : 0);
+    }
+  }
+  return 0;
+}
+
+// Grid = CUs x 2 blocks (queried once), capped by the tile count and by
+// GDLJ_DGRAD_PERSIST_BLOCKS (re-read per call; lets small problems make
+// one block walk several tiles).
+void launch_conv_dgrad_direct_p(const void* dy, const void* Wt, void* dx,
+                                const void* y0, float* part,
+                                const float* bias_fwd, float* stats_part,
+                                const void* zp, int Nb, int H, int W,
+                                int C8, int Ho, int Wo, int Ko8, long ldw,
+                                int R, int S, int pad, int act, float slope,
+                                int flag, hipStream_t s) {
+  using namespace cdd;
+  const int bm = (flag & PF_BM64) ? 64 : 128;
+  const int qsplit = (flag & PF_QSPLIT) ? 1 : 0;
+  const int lds_b = flag & PF_LDS_MASK;
+  int Hc = H / 2, Wc = W / 2;
+  int rows_c = bm / Wc;
+  int rgn_rows = p_axis_extent(rows_c, pad, R, qsplit != 0);
+  int rgn_cols = p_axis_extent(Wc, pad, S, false);
+  cdd_set_attrs_once();
+  static int ncu = 0;
+  if (ncu == 0) {
+    int dev = 0, v = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount,
+                              dev) != hipSuccess || v <= 0)
+      v = 256;
+    ncu = v;
+  }
+  long ntiles = (long)Nb * Hc * Wc / bm * (qsplit ? 2 : 1);
+  long nblk = std::min<long>(ntiles, (long)ncu * 2);
+  if (const char* e = getenv("GDLJ_DGRAD_PERSIST_BLOCKS")) {
+    long cap = atol(e);
+    if (cap > 0) nblk = std::min(nblk, cap);
+  }
+  if (nblk <= 0) return;
+  dim3 grid((unsigned)nblk);
+#define CDD_P_LAUNCH2(MI_, NCT_, PACT_)                                     \
+  hipLaunchKernelGGL((conv_dgrad_direct_p<MI_, NCT_, PACT_>), grid,         \
+                     dim3(256),                                             \
+                     lds_b, s, (const unsigned short*)dy,                   \
+                     (const unsigned short*)Wt, (unsigned short*)dx,        \
+                     (const unsigned short*)y0, part, bias_fwd, stats_part, \
+                     (const unsigned short*)zp, H, W, C8, Ho, Wo, Ko8, ldw, \
+                     R, S, pad, act, slope, Hc, Wc, rgn_rows, rgn_cols,     \
+                     make_fastdiv(Wc), (int)ntiles, qsplit)
+#define CDD_P_LAUNCH(MI_, NCT_)                                             \
+  do {                                                                      \
+    if (y0 != nullptr) CDD_P_LAUNCH2(MI_, NCT_, true);                      \
+    else CDD_P_LAUNCH2(MI_, NCT_, false);                                   \
+  } while (0)
+  if (bm == 128 && C8 == 64) CDD_P_LAUNCH(2, 1);
+  else if (bm == 128) CDD_P_LAUNCH(2, 2);
+  else if (C8 == 64) CDD_P_LAUNCH(1, 1);
+  else CDD_P_LAUNCH(1, 2);
+#undef CDD_P_LAUNCH
+#undef CDD_P_LAUNCH2
+}
 
 // Returns the LDS bytes needed when eligible (sign flags BM: positive
 // => BM=128, negative magnitude => BM=64), else 0.
@@ -358,16 +884,7 @@ void launch_conv_dgrad_direct(const void* dy, const void* Wt, void* dx,
   int rows_c = bm / Wc;
   int rgn_rows = rows_c + ((R + 1) >> 1) - 1;
   int rgn_cols = Wc + ((S + 1) >> 1) - 1;
-  static int attr_done = 0;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&conv_dgrad_direct<2>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&conv_dgrad_direct<1>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
-    attr_done = 1;
-  }
+  cdd_set_attrs_once();
   dim3 grid((long)Nb * Hc * Wc / bm, C8 / 64, 4);
   if (bm == 128)
     hipLaunchKernelGGL((conv_dgrad_direct<2>), grid, dim3(256), lds_b, s,

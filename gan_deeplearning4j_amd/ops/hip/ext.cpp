@@ -74,6 +74,13 @@ void launch_conv_dgrad_direct(const void*, const void*, void*, const void*,
                               float*, const float*, float*, const void*,
                               int, int, int, int, int, int, int, long, int,
                               int, int, int, float, int, hipStream_t);
+int conv_dgrad_direct_p_eligible(int, int, int, int, long, int, int, int,
+                                 int);
+void launch_conv_dgrad_direct_p(const void*, const void*, void*,
+                                const void*, float*, const float*, float*,
+                                const void*, int, int, int, int, int, int,
+                                int, long, int, int, int, int, float, int,
+                                hipStream_t);
 int launch_col2im_stats(const void*, void*, ConvGeom, const float*, int,
                         float, float*, hipStream_t);
 void launch_gemm_nt(const void*, const void*, float*, int, int, int, long,
@@ -435,6 +442,14 @@ std::vector<torch::Tensor> col2im_dact(
   return {out, db};
 }
 
+// GDLJ_DGRAD_PERSIST=0 routes the direct dgrad / convT forward to the
+// one-shot kernel instead of the persistent class-fused one (re-read
+// per call, like the other gates).
+static bool dgrad_persist_on() {
+  const char* e = getenv("GDLJ_DGRAD_PERSIST");
+  return !(e != nullptr && e[0] == '0' && e[1] == '\0');
+}
+
 // Direct parity-decomposed strided dgrad (conv_dgrad_direct.hip):
 // replaces dcol GEMM + col2im(_dact) when eligible.  dpre is the 2D
 // post-act-bwd gradient [N*Ho*Wo][Ko8]; wt the [R*S*C8][ldw] transposed
@@ -450,10 +465,18 @@ std::vector<torch::Tensor> conv_dgrad_direct(
   check_bf16(wt, "wt");
   int64_t Ko8 = dpre.size(1);
   long ldw = (long)wt.size(1);
-  int el = conv_dgrad_direct_eligible((int)H, (int)W, (int)C8, (int)Ko8,
-                                      ldw, (int)R, (int)S, (int)stride,
-                                      (int)pad);
-  if (el == 0) return {};
+  int elp = dgrad_persist_on()
+                ? conv_dgrad_direct_p_eligible((int)H, (int)W, (int)C8,
+                                               (int)Ko8, ldw, (int)R,
+                                               (int)S, (int)stride,
+                                               (int)pad)
+                : 0;
+  int el = elp != 0 ? 0
+                    : conv_dgrad_direct_eligible((int)H, (int)W, (int)C8,
+                                                 (int)Ko8, ldw, (int)R,
+                                                 (int)S, (int)stride,
+                                                 (int)pad);
+  if (elp == 0 && el == 0) return {};
   TORCH_CHECK(dpre.size(0) == N * Ho * Wo, "dpre rows");
   TORCH_CHECK(wt.size(0) >= R * S * C8, "wt rows");
   auto st = cur_stream();
@@ -472,12 +495,11 @@ std::vector<torch::Tensor> conv_dgrad_direct(
       db = torch::empty({C8}, f32);
     }
   }
-  launch_conv_dgrad_direct(dpre.data_ptr(), wt.data_ptr(), out.data_ptr(),
-                           y0p, part_p, nullptr, nullptr,
-                           zero_page.data_ptr(), (int)N, (int)H, (int)W,
-                           (int)C8, (int)Ho, (int)Wo, (int)Ko8, ldw,
-                           (int)R, (int)S, (int)pad, (int)act,
-                           (float)slope, el, st);
+  (elp != 0 ? launch_conv_dgrad_direct_p : launch_conv_dgrad_direct)(
+      dpre.data_ptr(), wt.data_ptr(), out.data_ptr(), y0p, part_p, nullptr,
+      nullptr, zero_page.data_ptr(), (int)N, (int)H, (int)W, (int)C8,
+      (int)Ho, (int)Wo, (int)Ko8, ldw, (int)R, (int)S, (int)pad, (int)act,
+      (float)slope, elp != 0 ? elp : el, st);
   if (part_p != nullptr) {
     launch_col_sum_sum2(part_p, 2048, (int)C8, db.data_ptr<float>(), st);
     return {out, db};
@@ -500,10 +522,18 @@ std::vector<torch::Tensor> conv_transpose_fwd_direct(
   check_bf16(w2a, "w2a");
   int64_t Kin = x2d.size(1);       // padded Cin = contraction K
   long ldw = (long)w2a.size(1);
-  int el = conv_dgrad_direct_eligible((int)Ho, (int)Wo, (int)Co8, (int)Kin,
-                                      ldw, (int)R, (int)S, (int)stride,
-                                      (int)pad);
-  if (el == 0) return {};
+  int elp = dgrad_persist_on()
+                ? conv_dgrad_direct_p_eligible((int)Ho, (int)Wo, (int)Co8,
+                                               (int)Kin, ldw, (int)R,
+                                               (int)S, (int)stride,
+                                               (int)pad)
+                : 0;
+  int el = elp != 0 ? 0
+                    : conv_dgrad_direct_eligible((int)Ho, (int)Wo, (int)Co8,
+                                                 (int)Kin, ldw, (int)R,
+                                                 (int)S, (int)stride,
+                                                 (int)pad);
+  if (elp == 0 && el == 0) return {};
   TORCH_CHECK(x2d.size(0) == N * Hi * Wi, "x2d rows");
   TORCH_CHECK(w2a.size(0) >= R * S * Co8, "w2a rows");
   auto st = cur_stream();
@@ -530,12 +560,11 @@ std::vector<torch::Tensor> conv_transpose_fwd_direct(
     ssum = torch::empty({Co8}, f32);
     ssq = torch::empty({Co8}, f32);
   }
-  launch_conv_dgrad_direct(x2d.data_ptr(), w2a.data_ptr(), y.data_ptr(),
-                           nullptr, nullptr, bias_p, stats_p,
-                           zero_page.data_ptr(), (int)N, (int)Ho, (int)Wo,
-                           (int)Co8, (int)Hi, (int)Wi, (int)Kin, ldw,
-                           (int)R, (int)S, (int)pad, (int)act,
-                           (float)slope, el, st);
+  (elp != 0 ? launch_conv_dgrad_direct_p : launch_conv_dgrad_direct)(
+      x2d.data_ptr(), w2a.data_ptr(), y.data_ptr(), nullptr, nullptr,
+      bias_p, stats_p, zero_page.data_ptr(), (int)N, (int)Ho, (int)Wo,
+      (int)Co8, (int)Hi, (int)Wi, (int)Kin, ldw, (int)R, (int)S, (int)pad,
+      (int)act, (float)slope, elp != 0 ? elp : el, st);
   if (stats_p != nullptr) {
     launch_bn_stats_sum2(stats_p, 2048, (int)Co8, ssum.data_ptr<float>(),
                          ssq.data_ptr<float>(), st);
@@ -1174,6 +1203,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           "direct parity-decomposed strided dgrad ({} when ineligible)");
   mod.def("conv_transpose_fwd_direct", &conv_transpose_fwd_direct,
           "strided convT forward via the parity-direct kernel");
+  mod.def("conv_dgrad_direct_p_eligible",
+          [](int64_t H, int64_t W, int64_t C8, int64_t Ko8, int64_t ldw,
+             int64_t R, int64_t S, int64_t stride, int64_t pad) {
+            return conv_dgrad_direct_p_eligible(
+                (int)H, (int)W, (int)C8, (int)Ko8, (long)ldw, (int)R,
+                (int)S, (int)stride, (int)pad);
+          },
+          "nonzero when the persistent direct dgrad takes this geometry");
   mod.def("fused_adam", &fused_adam);
   mod.def("fused_rmsprop", &fused_rmsprop);
   mod.def("csv_load", &csv_load, "multithreaded CSV -> fp32 tensor");
