@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include "launch_abi.h"
+
 #define DEV_INLINE __device__ __forceinline__
 
 // ---------------------------------------------------------------- vectors
@@ -73,26 +75,7 @@ DEV_INLINE float wave_reduce_max(float v) {
 constexpr int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // ------------------------------------------------- fast integer division
-// Granlund-Montgomery round-up magic; exact for 0 <= n < 2^30, 1 <= d < 2^16.
-// mul is 64-bit: for power-of-two (and small) divisors ceil(2^(32+l)/d)
-// exceeds 32 bits.
-struct FastDiv {
-  unsigned long long mul;
-  int shift;  // = 32 + ceil(log2 d)
-  int d;
-};
-
-inline FastDiv make_fastdiv(int d) {
-  int l = 0;
-  while ((1 << l) < d) ++l;
-  FastDiv f;
-  f.shift = 32 + l;
-  f.mul = ((1ULL << (32 + l)) + (unsigned long long)d - 1) /
-          (unsigned long long)d;
-  f.d = d;
-  return f;
-}
-
+// device side of FastDiv (launch_abi.h)
 DEV_INLINE unsigned fdiv(unsigned n, FastDiv f) {
   return (unsigned)(((unsigned long long)n * f.mul) >> f.shift);
 }
@@ -100,27 +83,6 @@ DEV_INLINE unsigned fdiv(unsigned n, FastDiv f) {
 DEV_INLINE unsigned fmod_(unsigned n, FastDiv f, unsigned q) {
   return n - q * (unsigned)f.d;
 }
-
-// Conv gather geometry for implicit-GEMM staging: maps an im2col
-// coordinate (np, k) to an input-image address without materializing col.
-// mode 0 (forward):    src pixel = grid_pos * stride - pad + (r,s)
-// mode 1 (transposed): src pixel = (grid_pos + pad - (r,s)) / stride,
-//                      valid only when divisible (conv dgrad / convT fwd)
-// mode 2 (parity class of a stride-2 transposed conv): the GEMM covers one
-//   (qh,qw) output-parity class; R,S are the per-class tap counts and
-//   (r,s) taps map to src pixel (grid_pos + off - tap); output rows
-//   scatter back to the full image via (oH,oW,oqh,oqw) in the epilogue.
-//   Every tap is valid (no 4x zero-padding like mode 1 at stride 2).
-struct ConvGather {
-  int N, H, W, C;        // source image dims (NHWC)
-  int Ho, Wo;            // patch grid (mode 2: the class grid)
-  int R, S, stride, pad;
-  int rsc;               // R*S*C (valid k range; >= rsc is zero padding)
-  int mode;
-  int off_h, off_w;      // mode 2: ho = hi2 + off - r2
-  int oH, oW, oqh, oqw;  // mode 2: output scatter (full dims + class)
-  FastDiv fC, fS, fWo, fHo, fStride;
-};
 
 #define HIP_CHECK_LAST()                                                     \
   do {                                                                       \

@@ -73,22 +73,27 @@ DEV_INLINE bf16x8 cdd_wfrag(const char* lds, int row, int kslot) {
   return *(const bf16x8*)(lds + byte);
 }
 
+// Blocks add their partials into row blockIdx.x & (kPartRows - 1) of the
+// bindings' [kPartRows][...] buffers (the one-shot grid can exceed kPartRows).
+static_assert((kPartRows & (kPartRows - 1)) == 0,
+              "kPartRows must be a power of two");
+
 // MI = pixel fragments per wave (BM = MI * 64).
 //
 // The same kernel serves the strided TRANSPOSED-conv forward (G side):
 // y[ho,wo,co] = sum over parity-valid taps of x[(ho+p-r)/2][ci] *
 // W[ci,co,r,s] is the identical gather; pass x as `dy`, the
 // [R*S*Co8][Cin] "w2a" pack as `Wt`, bias_fwd + act for the fused
-// epilogue, and stats_part ([2048][2*C8]) for fused BN statistics.
+// epilogue, and stats_part ([kPartRows][2*C8]) for fused BN statistics.
 template <int MI>
 __global__ __launch_bounds__(256, 2) void conv_dgrad_direct(
     const unsigned short* __restrict__ dy,   // [N][Ho][Wo][Ko8]
     const unsigned short* __restrict__ Wt,   // [R*S*C8][ldw], k = co
     unsigned short* __restrict__ dx,         // [N][H][W][C8]
     const unsigned short* __restrict__ y0,   // producer act out (or null)
-    float* __restrict__ part,                // [2048][C8] f32 (or null)
+    float* __restrict__ part,                // [kPartRows][C8] f32 (or null)
     const float* __restrict__ bias_fwd,      // convT fwd bias (or null)
-    float* __restrict__ stats_part,          // [2048][2*C8] f32 (or null)
+    float* __restrict__ stats_part,          // [kPartRows][2*C8] f32 (or null)
     const unsigned short* __restrict__ zp,   // 16B zero page
     int Nb, int H, int W, int C8, int Ho, int Wo, int Ko8, long ldw,
     int R, int S, int pad, int act, float slope,
@@ -317,10 +322,11 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct(
     __syncthreads();  // red is reused by the next reduction
   };
   if (y0 != nullptr && part != nullptr)
-    reduce_and_add(bsum,
-                   part + (long)(blockIdx.x & 2047) * C8 + cy * 64);
+    reduce_and_add(
+        bsum, part + (long)(blockIdx.x & (kPartRows - 1)) * C8 + cy * 64);
   if (stats_part != nullptr) {
-    float* srow = stats_part + (long)(blockIdx.x & 2047) * 2 * C8;
+    float* srow =
+        stats_part + (long)(blockIdx.x & (kPartRows - 1)) * 2 * C8;
     reduce_and_add(ssum, srow + cy * 64);
     reduce_and_add(ssq, srow + C8 + cy * 64);
   }
@@ -379,9 +385,9 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
     const unsigned short* __restrict__ Wt,   // [R*S*C8][ldw], k = co
     unsigned short* __restrict__ dx,         // [N][H][W][C8]
     const unsigned short* __restrict__ y0,   // producer act out (or null)
-    float* __restrict__ part,                // [2048][C8] f32 (or null)
+    float* __restrict__ part,                // [kPartRows][C8] f32 (or null)
     const float* __restrict__ bias_fwd,      // convT fwd bias (or null)
-    float* __restrict__ stats_part,          // [2048][2*C8] f32 (or null)
+    float* __restrict__ stats_part,          // [kPartRows][2*C8] f32 (or null)
     const unsigned short* __restrict__ zp,   // 16B zero page
     int H, int W, int C8, int Ho, int Wo, int Ko8, long ldw,
     int R, int S, int pad, int act, float slope,
@@ -701,10 +707,11 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
   #pragma unroll
   for (int k = 0; k < NCT; ++k) {
     if (PACT && part != nullptr)
-      reduce_and_add(bsum[k],
-                     part + (long)(blockIdx.x & 2047) * C8 + k * 64);
+      reduce_and_add(
+          bsum[k], part + (long)(blockIdx.x & (kPartRows - 1)) * C8 + k * 64);
     if (stats_part != nullptr) {
-      float* srow = stats_part + (long)(blockIdx.x & 2047) * 2 * C8;
+      float* srow =
+          stats_part + (long)(blockIdx.x & (kPartRows - 1)) * 2 * C8;
       reduce_and_add(ssum[k], srow + k * 64);
       reduce_and_add(ssq[k], srow + C8 + k * 64);
     }
@@ -734,10 +741,6 @@ static void cdd_set_attrs_once() {
 }
 
 namespace cdd {
-constexpr int PF_BM64 = 1 << 24;    // flag bits above the LDS byte count
-constexpr int PF_QSPLIT = 1 << 25;
-constexpr int PF_LDS_MASK = (1 << 24) - 1;
-
 // host mirror of the per-axis class geometry
 inline void p_axis_window(int pad, int R, int q, int* lo, int* hi) {
   int t0 = (q + pad) & 1;
@@ -755,24 +758,21 @@ inline int p_axis_extent(int len, int pad, int R, bool qsplit) {
   if (qsplit) return len + std::max(h0 - l0, h1 - l1);
   return len + std::max(h0, h1) - std::min(l0, l1);
 }
-}  // namespace cdd
 
-extern "C" {
-
-// Persistent kernel eligibility: 0, or LDS bytes | PF_* flags.  On top
-// of the one-shot kernel's conditions: C8 <= 128 (register partials
-// per c-tile), Ko8 a power of two (shift/mask cell decode), and the
-// union region + 32 KiB W double buffer within 80 KiB (two blocks per
-// CU).  Full four-class fusion is preferred; where its region is too
-// large the tile is split by row parity (two classes per staging).
-int conv_dgrad_direct_p_eligible(int H, int W, int C8, int Ko8, long ldw,
-                                 int R, int S, int stride, int pad) {
-  using namespace cdd;
+// Persistent kernel eligibility ({} is kind 0: not taken).  On top of the
+// one-shot kernel's conditions: C8 <= 128 (register partials per c-tile),
+// Ko8 a power of two (shift/mask cell decode), and the union region +
+// 32 KiB W double buffer within 80 KiB (two blocks per CU).  Full
+// four-class fusion is preferred; where its region is too large the tile
+// is split by row parity (two classes per staging).
+static DgradDirectPlan plan_persistent(int H, int W, int C8, int Ko8,
+                                       long ldw, int R, int S, int stride,
+                                       int pad) {
   if (stride != 2 || (C8 != 64 && C8 != 128) || Ko8 % 128 != 0 ||
       (Ko8 & (Ko8 - 1)) != 0 || ldw != Ko8)
-    return 0;
-  if (R < 2 || S < 2 || R > 8 || S > 8 || (H & 1) || (W & 1)) return 0;
-  if (pad < 0) return 0;
+    return {};
+  if (R < 2 || S < 2 || R > 8 || S > 8 || (H & 1) || (W & 1)) return {};
+  if (pad < 0) return {};
   int Hc = H / 2, Wc = W / 2;
   for (int bm : {128, 64}) {
     if (Wc > bm || bm % Wc != 0 || (Hc * Wc) % bm != 0) continue;
@@ -782,79 +782,18 @@ int conv_dgrad_direct_p_eligible(int H, int W, int C8, int Ko8, long ldw,
       int rgn_cols = p_axis_extent(Wc, pad, S, false);
       int lds_b = rgn_rows * rgn_cols * Ko8 * 2 + WBUF_B;
       if (lds_b > 80 * 1024) continue;
-      return lds_b | (bm == 64 ? PF_BM64 : 0) | (qsplit ? PF_QSPLIT : 0);
+      return DgradDirectPlan{2, bm, qsplit, lds_b};
     }
   }
-  return 0;
+  return {};
 }
 
-// Grid = CUs x 2 blocks (queried once), capped by the tile count and by
-// GDLJ_DGRAD_PERSIST_BLOCKS (re-read per call; lets small problems make
-// one block walk several tiles).
-void launch_conv_dgrad_direct_p(const void* dy, const void* Wt, void* dx,
-                                const void* y0, float* part,
-                                const float* bias_fwd, float* stats_part,
-                                const void* zp, int Nb, int H, int W,
-                                int C8, int Ho, int Wo, int Ko8, long ldw,
-                                int R, int S, int pad, int act, float slope,
-                                int flag, hipStream_t s) {
-  using namespace cdd;
-  const int bm = (flag & PF_BM64) ? 64 : 128;
-  const int qsplit = (flag & PF_QSPLIT) ? 1 : 0;
-  const int lds_b = flag & PF_LDS_MASK;
-  int Hc = H / 2, Wc = W / 2;
-  int rows_c = bm / Wc;
-  int rgn_rows = p_axis_extent(rows_c, pad, R, qsplit != 0);
-  int rgn_cols = p_axis_extent(Wc, pad, S, false);
-  cdd_set_attrs_once();
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount,
-                              dev) != hipSuccess || v <= 0)
-      v = 256;
-    ncu = v;
-  }
-  long ntiles = (long)Nb * Hc * Wc / bm * (qsplit ? 2 : 1);
-  long nblk = std::min<long>(ntiles, (long)ncu * 2);
-  if (const char* e = getenv("GDLJ_DGRAD_PERSIST_BLOCKS")) {
-    long cap = atol(e);
-    if (cap > 0) nblk = std::min(nblk, cap);
-  }
-  if (nblk <= 0) return;
-  dim3 grid((unsigned)nblk);
-#define CDD_P_LAUNCH2(MI_, NCT_, PACT_)                                     \
-  hipLaunchKernelGGL((conv_dgrad_direct_p<MI_, NCT_, PACT_>), grid,         \
-                     dim3(256),                                             \
-                     lds_b, s, (const unsigned short*)dy,                   \
-                     (const unsigned short*)Wt, (unsigned short*)dx,        \
-                     (const unsigned short*)y0, part, bias_fwd, stats_part, \
-                     (const unsigned short*)zp, H, W, C8, Ho, Wo, Ko8, ldw, \
-                     R, S, pad, act, slope, Hc, Wc, rgn_rows, rgn_cols,     \
-                     make_fastdiv(Wc), (int)ntiles, qsplit)
-#define CDD_P_LAUNCH(MI_, NCT_)                                             \
-  do {                                                                      \
-    if (y0 != nullptr) CDD_P_LAUNCH2(MI_, NCT_, true);                      \
-    else CDD_P_LAUNCH2(MI_, NCT_, false);                                   \
-  } while (0)
-  if (bm == 128 && C8 == 64) CDD_P_LAUNCH(2, 1);
-  else if (bm == 128) CDD_P_LAUNCH(2, 2);
-  else if (C8 == 64) CDD_P_LAUNCH(1, 1);
-  else CDD_P_LAUNCH(1, 2);
-#undef CDD_P_LAUNCH
-#undef CDD_P_LAUNCH2
-}
-
-// Returns the LDS bytes needed when eligible (sign flags BM: positive
-// => BM=128, negative magnitude => BM=64), else 0.
-int conv_dgrad_direct_eligible(int H, int W, int C8, int Ko8, long ldw,
-                               int R, int S, int stride, int pad) {
-  using namespace cdd;
+static DgradDirectPlan plan_oneshot(int H, int W, int C8, int Ko8, long ldw,
+                                    int R, int S, int stride) {
   if (stride != 2 || C8 % 64 != 0 || Ko8 % 128 != 0 || ldw != Ko8)
-    return 0;
+    return {};
   // R,S >= 2 keeps every parity class's tap set non-empty (Rc,Sc >= 1)
-  if (R < 2 || S < 2 || R > 8 || S > 8 || (H & 1) || (W & 1)) return 0;
+  if (R < 2 || S < 2 || R > 8 || S > 8 || (H & 1) || (W & 1)) return {};
   int Hc = H / 2, Wc = W / 2;
   for (int bm : {128, 64}) {
     if (Wc > bm || bm % Wc != 0 || (Hc * Wc) % bm != 0) continue;
@@ -865,43 +804,110 @@ int conv_dgrad_direct_eligible(int H, int W, int C8, int Ko8, long ldw,
     // slower than their dcol path (stage latency unhidden)
     int lds_b = rgn_rows * rgn_cols * Ko8 * 2 + WBUF_B;
     if (lds_b > 80 * 1024) continue;
-    return bm == 128 ? lds_b : -lds_b;
+    return DgradDirectPlan{1, bm, 0, lds_b};
   }
-  return 0;
+  return {};
 }
 
-void launch_conv_dgrad_direct(const void* dy, const void* Wt, void* dx,
-                              const void* y0, float* part,
-                              const float* bias_fwd, float* stats_part,
-                              const void* zp, int Nb, int H, int W, int C8,
-                              int Ho, int Wo, int Ko8, long ldw, int R,
-                              int S, int pad, int act, float slope,
-                              int lds_flag, hipStream_t s) {
-  using namespace cdd;
-  int bm = lds_flag > 0 ? 128 : 64;
-  int lds_b = lds_flag > 0 ? lds_flag : -lds_flag;
-  int Hc = H / 2, Wc = W / 2;
+// Grid = CUs x 2 blocks (queried once), capped by the tile count and by
+// GDLJ_DGRAD_PERSIST_BLOCKS (re-read per call; lets small problems make
+// one block walk several tiles).
+static void launch_persistent(const DgradDirectArgs& a, DgradDirectPlan plan,
+                              hipStream_t s) {
+  const int bm = plan.bm, qsplit = plan.qsplit, lds_b = plan.lds_bytes;
+  int Hc = a.H / 2, Wc = a.W / 2;
   int rows_c = bm / Wc;
-  int rgn_rows = rows_c + ((R + 1) >> 1) - 1;
-  int rgn_cols = Wc + ((S + 1) >> 1) - 1;
+  int rgn_rows = p_axis_extent(rows_c, a.pad, a.R, qsplit != 0);
+  int rgn_cols = p_axis_extent(Wc, a.pad, a.S, false);
   cdd_set_attrs_once();
-  dim3 grid((long)Nb * Hc * Wc / bm, C8 / 64, 4);
-  if (bm == 128)
-    hipLaunchKernelGGL((conv_dgrad_direct<2>), grid, dim3(256), lds_b, s,
-                       (const unsigned short*)dy, (const unsigned short*)Wt,
-                       (unsigned short*)dx, (const unsigned short*)y0, part,
-                       bias_fwd, stats_part,
-                       (const unsigned short*)zp, Nb, H, W, C8, Ho, Wo, Ko8,
-                       ldw, R, S, pad, act, slope, Hc, Wc, rows_c, rgn_rows,
-                       rgn_cols, make_fastdiv(Wc));
-  else
-    hipLaunchKernelGGL((conv_dgrad_direct<1>), grid, dim3(256), lds_b, s,
-                       (const unsigned short*)dy, (const unsigned short*)Wt,
-                       (unsigned short*)dx, (const unsigned short*)y0, part,
-                       bias_fwd, stats_part,
-                       (const unsigned short*)zp, Nb, H, W, C8, Ho, Wo, Ko8,
-                       ldw, R, S, pad, act, slope, Hc, Wc, rows_c, rgn_rows,
-                       rgn_cols, make_fastdiv(Wc));
+  static int ncu = 0;
+  if (ncu == 0) {
+    int dev = 0, v = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount,
+                              dev) != hipSuccess || v <= 0)
+      v = 256;
+    ncu = v;
+  }
+  long ntiles = (long)a.Nb * Hc * Wc / bm * (qsplit ? 2 : 1);
+  long nblk = std::min<long>(ntiles, (long)ncu * 2);
+  if (const char* e = getenv("GDLJ_DGRAD_PERSIST_BLOCKS")) {
+    long cap = atol(e);
+    if (cap > 0) nblk = std::min(nblk, cap);
+  }
+  if (nblk <= 0) return;
+  dim3 grid((unsigned)nblk);
+#define CDD_P_LAUNCH2(MI_, NCT_, PACT_)                                     \
+  hipLaunchKernelGGL((conv_dgrad_direct_p<MI_, NCT_, PACT_>), grid,         \
+                     dim3(256), lds_b, s, (const unsigned short*)a.dy,      \
+                     (const unsigned short*)a.Wt, (unsigned short*)a.dx,    \
+                     (const unsigned short*)a.y0, a.part, a.bias_fwd,       \
+                     a.stats_part, (const unsigned short*)a.zp, a.H, a.W,   \
+                     a.C8, a.Ho, a.Wo, a.Ko8, a.ldw, a.R, a.S, a.pad,       \
+                     a.act, a.slope, Hc, Wc, rgn_rows, rgn_cols,            \
+                     make_fastdiv(Wc), (int)ntiles, qsplit)
+#define CDD_P_LAUNCH(MI_, NCT_)                                             \
+  do {                                                                      \
+    if (a.y0 != nullptr) CDD_P_LAUNCH2(MI_, NCT_, true);                    \
+    else CDD_P_LAUNCH2(MI_, NCT_, false);                                   \
+  } while (0)
+  if (bm == 128 && a.C8 == 64) CDD_P_LAUNCH(2, 1);
+  else if (bm == 128) CDD_P_LAUNCH(2, 2);
+  else if (a.C8 == 64) CDD_P_LAUNCH(1, 1);
+  else CDD_P_LAUNCH(1, 2);
+#undef CDD_P_LAUNCH
+#undef CDD_P_LAUNCH2
+}
+
+static void launch_oneshot(const DgradDirectArgs& a, DgradDirectPlan plan,
+                           hipStream_t s) {
+  const int bm = plan.bm, lds_b = plan.lds_bytes;
+  int Hc = a.H / 2, Wc = a.W / 2;
+  int rows_c = bm / Wc;
+  int rgn_rows = rows_c + ((a.R + 1) >> 1) - 1;
+  int rgn_cols = Wc + ((a.S + 1) >> 1) - 1;
+  cdd_set_attrs_once();
+  dim3 grid((long)a.Nb * Hc * Wc / bm, a.C8 / 64, 4);
+#define CDD_LAUNCH(MI_)                                                     \
+  hipLaunchKernelGGL((conv_dgrad_direct<MI_>), grid, dim3(256), lds_b, s,   \
+                     (const unsigned short*)a.dy,                           \
+                     (const unsigned short*)a.Wt, (unsigned short*)a.dx,    \
+                     (const unsigned short*)a.y0, a.part, a.bias_fwd,       \
+                     a.stats_part, (const unsigned short*)a.zp, a.Nb, a.H,  \
+                     a.W, a.C8, a.Ho, a.Wo, a.Ko8, a.ldw, a.R, a.S, a.pad,  \
+                     a.act, a.slope, Hc, Wc, rows_c, rgn_rows, rgn_cols,    \
+                     make_fastdiv(Wc))
+  if (bm == 128) CDD_LAUNCH(2);
+  else CDD_LAUNCH(1);
+#undef CDD_LAUNCH
+}
+}  // namespace cdd
+
+extern "C" {
+
+// GDLJ_DGRAD_PERSIST=0 routes the direct dgrad / convT forward to the
+// one-shot kernel instead of the persistent class-fused one (re-read
+// per call, like the other gates).
+int conv_dgrad_direct_persist_enabled() {
+  const char* e = getenv("GDLJ_DGRAD_PERSIST");
+  return !(e != nullptr && e[0] == '0' && e[1] == '\0');
+}
+
+DgradDirectPlan conv_dgrad_direct_plan(int H, int W, int C8, int Ko8,
+                                       long ldw, int R, int S, int stride,
+                                       int pad, int allow_persist) {
+  if (allow_persist) {
+    DgradDirectPlan p =
+        cdd::plan_persistent(H, W, C8, Ko8, ldw, R, S, stride, pad);
+    if (p.kind != 0) return p;
+  }
+  return cdd::plan_oneshot(H, W, C8, Ko8, ldw, R, S, stride);
+}
+
+void launch_conv_dgrad_direct(const DgradDirectArgs& a, DgradDirectPlan plan,
+                              hipStream_t s) {
+  if (plan.kind == 2) cdd::launch_persistent(a, plan, s);
+  else if (plan.kind == 1) cdd::launch_oneshot(a, plan, s);
 }
 
 }  // extern "C"

@@ -1,162 +1,18 @@
 // Torch bindings for the gfx950 kernel library (_C extension).
 // Thin layer: checks, allocation, stream plumbing; all compute is in the
-// .hip kernels. Built in-tree by setup.py (hipcc, --offload-arch=gfx950).
+// .hip kernels, reached through the launchers declared in launch_abi.h.
+// Built in-tree by setup.py (hipcc, --offload-arch=gfx950).
 
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
+#include "launch_abi.h"
+
 // csv_loader.cpp (native data loader)
 torch::Tensor csv_load(const std::string& path, int64_t skip_rows);
 
 namespace {
-
-struct ConvGeom {
-  int N, H, W, C, Ho, Wo, R, S, stride, pad, kpad;
-};
-struct PoolGeom {
-  int N, H, W, C, Ho, Wo, k, stride;
-};
-struct FastDiv {
-  unsigned long long mul;  // 64-bit: pow2 divisors overflow 32-bit magic
-  int shift;
-  int d;
-};
-struct ConvGather {
-  int N, H, W, C, Ho, Wo, R, S, stride, pad, rsc, mode;
-  int off_h, off_w, oH, oW, oqh, oqw;
-  FastDiv fC, fS, fWo, fHo, fStride;
-};
-
-static FastDiv make_fastdiv_h(int d) {
-  int l = 0;
-  while ((1 << l) < d) ++l;
-  FastDiv f;
-  f.shift = 32 + l;
-  f.mul = ((1ULL << (32 + l)) + (unsigned long long)d - 1) /
-          (unsigned long long)d;
-  f.d = d;
-  return f;
-}
-
-static ConvGather make_gather(int N, int H, int W, int C, int Ho, int Wo,
-                              int R, int S, int stride, int pad,
-                              int mode = 0) {
-  ConvGather g;
-  g.N = N; g.H = H; g.W = W; g.C = C; g.Ho = Ho; g.Wo = Wo;
-  g.R = R; g.S = S; g.stride = stride; g.pad = pad;
-  g.rsc = R * S * C;
-  g.mode = mode;
-  g.off_h = g.off_w = 0;
-  g.oH = g.oW = g.oqh = g.oqw = 0;
-  g.fC = make_fastdiv_h(C);
-  g.fS = make_fastdiv_h(S);
-  g.fWo = make_fastdiv_h(Wo);
-  g.fHo = make_fastdiv_h(Ho);
-  g.fStride = make_fastdiv_h(stride);
-  return g;
-}
-
-extern "C" {
-int launch_gemm_tn(const void*, const void*, void*, float*, const float*,
-                   int, int, int, long, long, int, float, float*,
-                   hipStream_t);
-int launch_gemm_tn_8p_tweak(int, const void*, const void*, void*, int, int,
-                            int, long, long, hipStream_t);
-int launch_gemm_tn_gather(const void*, const void*, void*, const float*,
-                          int, int, int, long, int, float, ConvGather,
-                          const void*, float*, hipStream_t);
-int launch_col2im_dact(const void*, void*, ConvGeom, const void*, int,
-                       float, float*, hipStream_t);
-int conv_dgrad_direct_eligible(int, int, int, int, long, int, int, int,
-                               int);
-void launch_conv_dgrad_direct(const void*, const void*, void*, const void*,
-                              float*, const float*, float*, const void*,
-                              int, int, int, int, int, int, int, long, int,
-                              int, int, int, float, int, hipStream_t);
-int conv_dgrad_direct_p_eligible(int, int, int, int, long, int, int, int,
-                                 int);
-void launch_conv_dgrad_direct_p(const void*, const void*, void*,
-                                const void*, float*, const float*, float*,
-                                const void*, int, int, int, int, int, int,
-                                int, long, int, int, int, int, float, int,
-                                hipStream_t);
-int launch_col2im_stats(const void*, void*, ConvGeom, const float*, int,
-                        float, float*, hipStream_t);
-void launch_gemm_nt(const void*, const void*, float*, int, int, int, long,
-                    long, int, int, ConvGather, const void*, hipStream_t);
-void launch_im2col(const void*, void*, ConvGeom, hipStream_t);
-void launch_col2im(const void*, void*, ConvGeom, const float*, int, float,
-                   hipStream_t);
-void launch_maxpool_fwd(const void*, void*, void*, PoolGeom, hipStream_t);
-void launch_maxpool_bwd(const void*, const void*, void*, PoolGeom,
-                        hipStream_t);
-void launch_upsample_fwd(const void*, void*, int, int, int, int, int,
-                         hipStream_t);
-void launch_upsample_bwd(const void*, void*, int, int, int, int, int,
-                         hipStream_t);
-void launch_act_fwd(const void*, void*, long, int, float, hipStream_t);
-void launch_act_bwd(const void*, const void*, void*, long, int, float,
-                    hipStream_t);
-void launch_col_sum(const void*, float*, long, int, hipStream_t);
-int dropout_grid_cap();
-int dropout_block_size();
-void launch_dropout_fwd(const void*, void*, void*, const void*, long,
-                        unsigned int, float, hipStream_t);
-void launch_dropout_bwd(const void*, const void*, void*, long, float,
-                        hipStream_t);
-void launch_gaussian_noise_fwd(const void*, void*, const void*, long, float,
-                               hipStream_t);
-void launch_bce_fwd(const void*, const void*, float*, long, hipStream_t);
-void launch_bce_bwd(const void*, const void*, void*, float, long, hipStream_t);
-void launch_softmax_xent_fwd(const void*, const void*, float*, void*, int,
-                             int, hipStream_t);
-void launch_softmax_xent_bwd(const void*, const void*, void*, float, long,
-                             hipStream_t);
-void launch_bn_stats(const void*, long, int, float*, float*, hipStream_t);
-int launch_bn_stats_part(const void*, long, int, float*, hipStream_t);
-void launch_bn_stats_sum2(const float*, int, int, float*, float*,
-                          hipStream_t);
-int launch_bn_bwd_reduce_part(const void*, const void*, long, int,
-                              const float*, const float*, float*,
-                              hipStream_t);
-void launch_bn_bwd_sum2(const float*, int, int, float*, float*, hipStream_t);
-int launch_col_sum_part(const void*, float*, long, int, hipStream_t);
-void launch_col_sum_sum2(const float*, int, int, float*, hipStream_t);
-int launch_act_bwd_bias(const void*, const void*, void*, float*, long, int,
-                        int, float, hipStream_t);
-void launch_bn_finalize(const float*, const float*, long, int, float, float,
-                        float*, float*, float*, float*, hipStream_t);
-void launch_bn_apply(const void*, void*, long, int, const float*,
-                     const float*, const float*, const float*, hipStream_t);
-void launch_bn_apply_eval(const void*, void*, long, int, const float*,
-                          const float*, const float*, const float*, float,
-                          hipStream_t);
-void launch_bn_bwd_reduce(const void*, const void*, long, int, const float*,
-                          const float*, float*, float*, hipStream_t);
-int launch_bn_bwd_apply_act(const void*, const void*, void*, long, int,
-                            const float*, const float*, const float*,
-                            const float*, const float*, int, float, float*,
-                            hipStream_t);
-void launch_bn_bwd_apply(const void*, const void*, void*, long, int,
-                         const float*, const float*, const float*,
-                         const float*, const float*, hipStream_t);
-void launch_fused_adam(void*, const void*, float*, float*, float*, long, int,
-                       int, float, float, float, float, float, float, int,
-                       const int*, hipStream_t);
-void launch_amax(const void*, long, unsigned*, hipStream_t);
-void launch_fp8_make_scale(const unsigned*, float*, float*, hipStream_t);
-void launch_quant_fp8(const void*, void*, long, const float*, hipStream_t);
-void launch_quant_fp8_delayed(const void*, void*, long, const float*,
-                              unsigned*, hipStream_t);
-void launch_fp8_roll_scale(unsigned*, float*, float*, hipStream_t);
-void launch_gemm_tn_fp8(const void*, const void*, void*, const float*,
-                        const float*, const float*, int, int, int, long,
-                        long, int, float, int, ConvGather, const void*,
-                        hipStream_t);
-void launch_fused_rmsprop(void*, const void*, float*, float*, long, int, int,
-                          float, float, float, float, float, hipStream_t);
-}
 
 hipStream_t cur_stream() {
   return (hipStream_t)at::cuda::getCurrentCUDAStream().stream();
@@ -174,6 +30,22 @@ void check_f32(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
+// Optional fp32 vector (bias): nullptr when absent / undefined / empty.
+const float* opt_f32_ptr(const c10::optional<torch::Tensor>& t,
+                         const char* name, int64_t min_numel = 0) {
+  if (!(t.has_value() && t->defined() && t->numel() > 0)) return nullptr;
+  check_f32(*t, name);
+  TORCH_CHECK(t->numel() >= min_numel, name, " length");
+  return t->data_ptr<float>();
+}
+
+ConvGeom conv_geom(int64_t N, int64_t H, int64_t W, int64_t C, int64_t Ho,
+                   int64_t Wo, int64_t R, int64_t S, int64_t stride,
+                   int64_t pad, int64_t kpad) {
+  return ConvGeom{(int)N, (int)H, (int)W, (int)C, (int)Ho, (int)Wo,
+                  (int)R, (int)S, (int)stride, (int)pad, (int)kpad};
+}
+
 // ------------------------------------------------------------------ GEMM
 torch::Tensor gemm_tn(torch::Tensor A, torch::Tensor B,
                       c10::optional<torch::Tensor> bias, int64_t act,
@@ -183,12 +55,8 @@ torch::Tensor gemm_tn(torch::Tensor A, torch::Tensor B,
   int64_t M = A.size(0), K = A.size(1), N = B.size(0);
   TORCH_CHECK(B.size(1) == K, "K mismatch");
   TORCH_CHECK(K % 64 == 0, "K must be padded to a multiple of 64, got ", K);
-  const float* bias_p = nullptr;
-  if (bias.has_value() && bias->defined() && bias->numel() > 0) {
-    check_f32(*bias, "bias");
-    TORCH_CHECK(bias->numel() == N, "bias size");
-    bias_p = bias->data_ptr<float>();
-  }
+  const float* bias_p = opt_f32_ptr(bias, "bias");
+  TORCH_CHECK(bias_p == nullptr || bias->numel() == N, "bias size");
   auto opts = A.options();
   torch::Tensor C = torch::empty(
       {M, N}, out_f32 ? opts.dtype(torch::kFloat32) : opts);
@@ -208,11 +76,7 @@ std::vector<torch::Tensor> gemm_tn_stats(torch::Tensor A, torch::Tensor B,
   check_bf16(B, "B");
   int64_t M = A.size(0), K = A.size(1), N = B.size(0);
   TORCH_CHECK(B.size(1) == K && K % 64 == 0 && N % 8 == 0);
-  const float* bias_p = nullptr;
-  if (bias.has_value() && bias->defined() && bias->numel() > 0) {
-    check_f32(*bias, "bias");
-    bias_p = bias->data_ptr<float>();
-  }
+  const float* bias_p = opt_f32_ptr(bias, "bias");
   auto f32 = A.options().dtype(torch::kFloat32);
   torch::Tensor C = torch::empty({M, N}, A.options());
   int64_t gx = (M + 127) / 128;
@@ -267,15 +131,11 @@ std::vector<torch::Tensor> conv_fwd_implicit(torch::Tensor x, torch::Tensor Wp,
   TORCH_CHECK(C % 8 == 0, "implicit conv needs C % 8 == 0");
   int64_t Kout = Wp.size(0), kpad = Wp.size(1);
   int64_t M = Nb * Ho * Wo;
-  const float* bias_p = nullptr;
-  if (bias.has_value() && bias->defined() && bias->numel() > 0) {
-    check_f32(*bias, "bias");
-    bias_p = bias->data_ptr<float>();
-  }
+  const float* bias_p = opt_f32_ptr(bias, "bias");
   torch::Tensor y = torch::empty({M, Kout}, x.options());
-  ConvGather g = make_gather((int)Nb, (int)H, (int)W, (int)C, (int)Ho,
-                             (int)Wo, (int)R, (int)S, (int)stride, (int)pad,
-                             (int)mode);
+  ConvGather g = make_conv_gather((int)Nb, (int)H, (int)W, (int)C, (int)Ho,
+                                  (int)Wo, (int)R, (int)S, (int)stride,
+                                  (int)pad, (int)mode);
   auto st = cur_stream();
   if (want_stats && Kout % 8 == 0) {
     auto f32 = x.options().dtype(torch::kFloat32);
@@ -310,10 +170,10 @@ torch::Tensor gemm_nt_implicit(torch::Tensor A, torch::Tensor B,
   TORCH_CHECK(d.numel() == 10 || d.numel() == 11,
               "img_dims = [N,H,W,C,Ho,Wo,R,S,stride,pad(,mode)]");
   const int64_t* p = d.data_ptr<int64_t>();
-  ConvGather g = make_gather((int)p[0], (int)p[1], (int)p[2], (int)p[3],
-                             (int)p[4], (int)p[5], (int)p[6], (int)p[7],
-                             (int)p[8], (int)p[9],
-                             d.numel() == 11 ? (int)p[10] : 0);
+  ConvGather g = make_conv_gather((int)p[0], (int)p[1], (int)p[2], (int)p[3],
+                                  (int)p[4], (int)p[5], (int)p[6], (int)p[7],
+                                  (int)p[8], (int)p[9],
+                                  d.numel() == 11 ? (int)p[10] : 0);
   torch::Tensor C =
       splitk > 1
           ? torch::zeros({Mdim, Ndim}, A.options().dtype(torch::kFloat32))
@@ -340,11 +200,7 @@ torch::Tensor conv_parity_implicit(
   check_bf16(img, "img");
   TORCH_CHECK(Cs % 8 == 0, "parity conv needs source C % 8 == 0");
   TORCH_CHECK((int64_t)wcls.size() == stride * stride, "one pack per class");
-  const float* bias_p = nullptr;
-  if (bias.has_value() && bias->defined() && bias->numel() > 0) {
-    check_f32(*bias, "bias");
-    bias_p = bias->data_ptr<float>();
-  }
+  const float* bias_p = opt_f32_ptr(bias, "bias");
   torch::Tensor y = torch::empty({Nb * oHd * oWd, Nout}, img.options());
   int s_ = (int)stride;
   for (int qh = 0; qh < s_; ++qh) {
@@ -359,8 +215,8 @@ torch::Tensor conv_parity_implicit(
       int Wq = (int)((oWd - qw + stride - 1) / stride);
       if (Hq <= 0 || Wq <= 0 || R2 <= 0 || S2 <= 0) continue;
       TORCH_CHECK(wq.size(0) == Nout, "pack Nout");
-      ConvGather g = make_gather((int)Nb, (int)Hs, (int)Ws, (int)Cs, Hq, Wq,
-                                 R2, S2, (int)stride, (int)pad, 2);
+      ConvGather g = make_conv_gather((int)Nb, (int)Hs, (int)Ws, (int)Cs, Hq,
+                                      Wq, R2, S2, (int)stride, (int)pad, 2);
       g.off_h = (int)((qh + pad - prh) / stride);
       g.off_w = (int)((qw + pad - prw) / stride);
       g.oH = (int)oHd;
@@ -383,8 +239,7 @@ torch::Tensor im2col(torch::Tensor x, int64_t N, int64_t H, int64_t W,
                      int64_t C, int64_t Ho, int64_t Wo, int64_t R, int64_t S,
                      int64_t stride, int64_t pad, int64_t kpad) {
   check_bf16(x, "x");
-  ConvGeom g{(int)N, (int)H, (int)W, (int)C, (int)Ho, (int)Wo,
-             (int)R, (int)S, (int)stride, (int)pad, (int)kpad};
+  ConvGeom g = conv_geom(N, H, W, C, Ho, Wo, R, S, stride, pad, kpad);
   torch::Tensor col = torch::empty({N * Ho * Wo, kpad}, x.options());
   launch_im2col(x.data_ptr(), col.data_ptr(), g, cur_stream());
   return col;
@@ -396,13 +251,8 @@ torch::Tensor col2im(torch::Tensor dcol, int64_t N, int64_t H, int64_t W,
                      c10::optional<torch::Tensor> bias, int64_t act,
                      double slope) {
   check_bf16(dcol, "dcol");
-  ConvGeom g{(int)N, (int)H, (int)W, (int)C, (int)Ho, (int)Wo,
-             (int)R, (int)S, (int)stride, (int)pad, (int)kpad};
-  const float* bias_p = nullptr;
-  if (bias.has_value() && bias->defined() && bias->numel() > 0) {
-    check_f32(*bias, "bias");
-    bias_p = bias->data_ptr<float>();
-  }
+  ConvGeom g = conv_geom(N, H, W, C, Ho, Wo, R, S, stride, pad, kpad);
+  const float* bias_p = opt_f32_ptr(bias, "bias");
   torch::Tensor out = torch::empty({N, H, W, C}, dcol.options());
   launch_col2im(dcol.data_ptr(), out.data_ptr(), g, bias_p, (int)act,
                 (float)slope, cur_stream());
@@ -421,8 +271,7 @@ std::vector<torch::Tensor> col2im_dact(
   check_bf16(y0, "y0");
   TORCH_CHECK(C % 8 == 0 && kpad % 8 == 0, "col2im_dact needs C,kpad %8==0");
   TORCH_CHECK(y0.numel() == N * H * W * C, "y0 shape");
-  ConvGeom g{(int)N, (int)H, (int)W, (int)C, (int)Ho, (int)Wo,
-             (int)R, (int)S, (int)stride, (int)pad, (int)kpad};
+  ConvGeom g = conv_geom(N, H, W, C, Ho, Wo, R, S, stride, pad, kpad);
   auto f32 = dcol.options().dtype(torch::kFloat32);
   torch::Tensor out = torch::empty({N, H, W, C}, dcol.options());
   torch::Tensor db = torch::empty({want_bias ? C : 0}, f32);
@@ -430,7 +279,7 @@ std::vector<torch::Tensor> col2im_dact(
   float* part_p = nullptr;
   auto s = cur_stream();
   if (want_bias) {
-    part = torch::empty({2048, C}, f32);
+    part = torch::empty({kPartRows, C}, f32);
     part_p = part.data_ptr<float>();
   }
   int gx = launch_col2im_dact(dcol.data_ptr(), out.data_ptr(), g,
@@ -442,12 +291,27 @@ std::vector<torch::Tensor> col2im_dact(
   return {out, db};
 }
 
-// GDLJ_DGRAD_PERSIST=0 routes the direct dgrad / convT forward to the
-// one-shot kernel instead of the persistent class-fused one (re-read
-// per call, like the other gates).
-static bool dgrad_persist_on() {
-  const char* e = getenv("GDLJ_DGRAD_PERSIST");
-  return !(e != nullptr && e[0] == '0' && e[1] == '\0');
+// Geometry of a direct parity-decomposed launch (conv_dgrad_direct.hip) in
+// the kernel's dgrad naming; the caller sets the pointers once it knows the
+// plan.  dgrad_direct_plan picks the kernel: kind 0 = ineligible (caller
+// falls back).  GDLJ_DGRAD_PERSIST=0 selects the one-shot kernel (read per
+// call on the launcher side).
+DgradDirectArgs dgrad_direct_args(int64_t N, int64_t H, int64_t W, int64_t C8,
+                                  int64_t Ho, int64_t Wo, int64_t Ko8,
+                                  int64_t ldw, int64_t R, int64_t S,
+                                  int64_t pad, int64_t act, double slope) {
+  DgradDirectArgs a{};
+  a.Nb = (int)N; a.H = (int)H; a.W = (int)W; a.C8 = (int)C8;
+  a.Ho = (int)Ho; a.Wo = (int)Wo; a.Ko8 = (int)Ko8; a.ldw = (long)ldw;
+  a.R = (int)R; a.S = (int)S; a.pad = (int)pad; a.act = (int)act;
+  a.slope = (float)slope;
+  return a;
+}
+
+DgradDirectPlan dgrad_direct_plan(const DgradDirectArgs& a, int64_t stride) {
+  return conv_dgrad_direct_plan(a.H, a.W, a.C8, a.Ko8, a.ldw, a.R, a.S,
+                                (int)stride, a.pad,
+                                conv_dgrad_direct_persist_enabled());
 }
 
 // Direct parity-decomposed strided dgrad (conv_dgrad_direct.hip):
@@ -463,45 +327,34 @@ std::vector<torch::Tensor> conv_dgrad_direct(
     int64_t pad, int64_t act, double slope, bool want_bias) {
   check_bf16(dpre, "dpre");
   check_bf16(wt, "wt");
-  int64_t Ko8 = dpre.size(1);
-  long ldw = (long)wt.size(1);
-  int elp = dgrad_persist_on()
-                ? conv_dgrad_direct_p_eligible((int)H, (int)W, (int)C8,
-                                               (int)Ko8, ldw, (int)R,
-                                               (int)S, (int)stride,
-                                               (int)pad)
-                : 0;
-  int el = elp != 0 ? 0
-                    : conv_dgrad_direct_eligible((int)H, (int)W, (int)C8,
-                                                 (int)Ko8, ldw, (int)R,
-                                                 (int)S, (int)stride,
-                                                 (int)pad);
-  if (elp == 0 && el == 0) return {};
+  DgradDirectArgs a = dgrad_direct_args(N, H, W, C8, Ho, Wo, dpre.size(1),
+                                        wt.size(1), R, S, pad, act, slope);
+  DgradDirectPlan plan = dgrad_direct_plan(a, stride);
+  if (plan.kind == 0) return {};
   TORCH_CHECK(dpre.size(0) == N * Ho * Wo, "dpre rows");
   TORCH_CHECK(wt.size(0) >= R * S * C8, "wt rows");
   auto st = cur_stream();
   torch::Tensor out = torch::empty({N, H, W, C8}, dpre.options());
-  const void* y0p = nullptr;
-  float* part_p = nullptr;
   torch::Tensor part, db;
   if (y0.has_value() && y0->defined()) {
     check_bf16(*y0, "y0");
     TORCH_CHECK(y0->numel() == N * H * W * C8, "y0 shape");
-    y0p = y0->data_ptr();
+    a.y0 = y0->data_ptr();
     if (want_bias) {
       auto f32 = dpre.options().dtype(torch::kFloat32);
-      part = torch::zeros({2048, C8}, f32);
-      part_p = part.data_ptr<float>();
+      part = torch::zeros({kPartRows, C8}, f32);
+      a.part = part.data_ptr<float>();
       db = torch::empty({C8}, f32);
     }
   }
-  (elp != 0 ? launch_conv_dgrad_direct_p : launch_conv_dgrad_direct)(
-      dpre.data_ptr(), wt.data_ptr(), out.data_ptr(), y0p, part_p, nullptr,
-      nullptr, zero_page.data_ptr(), (int)N, (int)H, (int)W, (int)C8,
-      (int)Ho, (int)Wo, (int)Ko8, ldw, (int)R, (int)S, (int)pad, (int)act,
-      (float)slope, elp != 0 ? elp : el, st);
-  if (part_p != nullptr) {
-    launch_col_sum_sum2(part_p, 2048, (int)C8, db.data_ptr<float>(), st);
+  a.dy = dpre.data_ptr();
+  a.Wt = wt.data_ptr();
+  a.dx = out.data_ptr();
+  a.zp = zero_page.data_ptr();
+  launch_conv_dgrad_direct(a, plan, st);
+  if (a.part != nullptr) {
+    launch_col_sum_sum2(a.part, kPartRows, (int)C8, db.data_ptr<float>(),
+                        st);
     return {out, db};
   }
   return {out};
@@ -520,54 +373,40 @@ std::vector<torch::Tensor> conv_transpose_fwd_direct(
     bool want_stats) {
   check_bf16(x2d, "x2d");
   check_bf16(w2a, "w2a");
-  int64_t Kin = x2d.size(1);       // padded Cin = contraction K
-  long ldw = (long)w2a.size(1);
-  int elp = dgrad_persist_on()
-                ? conv_dgrad_direct_p_eligible((int)Ho, (int)Wo, (int)Co8,
-                                               (int)Kin, ldw, (int)R,
-                                               (int)S, (int)stride,
-                                               (int)pad)
-                : 0;
-  int el = elp != 0 ? 0
-                    : conv_dgrad_direct_eligible((int)Ho, (int)Wo, (int)Co8,
-                                                 (int)Kin, ldw, (int)R,
-                                                 (int)S, (int)stride,
-                                                 (int)pad);
-  if (elp == 0 && el == 0) return {};
+  // roles swap: the kernel's H,W is this op's output, its Ho,Wo the input,
+  // its Ko8 the padded Cin (the contraction)
+  DgradDirectArgs a = dgrad_direct_args(N, Ho, Wo, Co8, Hi, Wi, x2d.size(1),
+                                        w2a.size(1), R, S, pad, act, slope);
+  DgradDirectPlan plan = dgrad_direct_plan(a, stride);
+  if (plan.kind == 0) return {};
   TORCH_CHECK(x2d.size(0) == N * Hi * Wi, "x2d rows");
   TORCH_CHECK(w2a.size(0) >= R * S * Co8, "w2a rows");
   auto st = cur_stream();
   torch::Tensor y = torch::empty({N, Ho, Wo, Co8}, x2d.options());
-  const float* bias_p = nullptr;
-  if (bias.has_value() && bias->defined() && bias->numel() > 0) {
-    check_f32(*bias, "bias");
-    TORCH_CHECK(bias->numel() >= Co8, "bias length");
-    bias_p = bias->data_ptr<float>();
-  }
+  a.bias_fwd = opt_f32_ptr(bias, "bias", Co8);
   torch::Tensor zero_bias;
-  if (bias_p == nullptr) {
+  if (a.bias_fwd == nullptr) {
     // the kernel keys "apply act_fwd" off the bias pointer
     zero_bias = torch::zeros({Co8},
                              x2d.options().dtype(torch::kFloat32));
-    bias_p = zero_bias.data_ptr<float>();
+    a.bias_fwd = zero_bias.data_ptr<float>();
   }
-  float* stats_p = nullptr;
   torch::Tensor part, ssum, ssq;
   if (want_stats) {
     auto f32 = x2d.options().dtype(torch::kFloat32);
-    part = torch::zeros({2048, 2 * Co8}, f32);
-    stats_p = part.data_ptr<float>();
+    part = torch::zeros({kPartRows, 2 * Co8}, f32);
+    a.stats_part = part.data_ptr<float>();
     ssum = torch::empty({Co8}, f32);
     ssq = torch::empty({Co8}, f32);
   }
-  (elp != 0 ? launch_conv_dgrad_direct_p : launch_conv_dgrad_direct)(
-      x2d.data_ptr(), w2a.data_ptr(), y.data_ptr(), nullptr, nullptr,
-      bias_p, stats_p, zero_page.data_ptr(), (int)N, (int)Ho, (int)Wo,
-      (int)Co8, (int)Hi, (int)Wi, (int)Kin, ldw, (int)R, (int)S, (int)pad,
-      (int)act, (float)slope, elp != 0 ? elp : el, st);
-  if (stats_p != nullptr) {
-    launch_bn_stats_sum2(stats_p, 2048, (int)Co8, ssum.data_ptr<float>(),
-                         ssq.data_ptr<float>(), st);
+  a.dy = x2d.data_ptr();
+  a.Wt = w2a.data_ptr();
+  a.dx = y.data_ptr();
+  a.zp = zero_page.data_ptr();
+  launch_conv_dgrad_direct(a, plan, st);
+  if (a.stats_part != nullptr) {
+    launch_bn_stats_sum2(a.stats_part, kPartRows, (int)Co8,
+                         ssum.data_ptr<float>(), ssq.data_ptr<float>(), st);
     return {y, ssum, ssq};
   }
   return {y};
@@ -581,16 +420,11 @@ std::vector<torch::Tensor> col2im_stats(
     int64_t act, double slope) {
   check_bf16(dcol, "dcol");
   TORCH_CHECK(C % 8 == 0 && kpad % 8 == 0);
-  ConvGeom g{(int)N, (int)H, (int)W, (int)C, (int)Ho, (int)Wo,
-             (int)R, (int)S, (int)stride, (int)pad, (int)kpad};
-  const float* bias_p = nullptr;
-  if (bias.has_value() && bias->defined() && bias->numel() > 0) {
-    check_f32(*bias, "bias");
-    bias_p = bias->data_ptr<float>();
-  }
+  ConvGeom g = conv_geom(N, H, W, C, Ho, Wo, R, S, stride, pad, kpad);
+  const float* bias_p = opt_f32_ptr(bias, "bias");
   auto f32 = dcol.options().dtype(torch::kFloat32);
   torch::Tensor out = torch::empty({N, H, W, C}, dcol.options());
-  torch::Tensor part = torch::empty({2048, 2 * C}, f32);
+  torch::Tensor part = torch::empty({kPartRows, 2 * C}, f32);
   torch::Tensor sum = torch::empty({C}, f32), sumsq = torch::empty({C}, f32);
   auto st = cur_stream();
   int gx = launch_col2im_stats(dcol.data_ptr(), out.data_ptr(), g, bias_p,
@@ -664,7 +498,7 @@ std::vector<torch::Tensor> act_bwd_bias(torch::Tensor dy,
   TORCH_CHECK(n % 8 == 0, "act_bwd_bias needs N % 8 == 0");
   auto f32 = dy.options().dtype(torch::kFloat32);
   torch::Tensor dx = torch::empty_like(dy);
-  torch::Tensor scratch = torch::empty({2048, n}, f32);
+  torch::Tensor scratch = torch::empty({kPartRows, n}, f32);
   torch::Tensor db = torch::empty({n}, f32);
   const void* y_p = nullptr;
   if (act != 0) {
@@ -762,7 +596,7 @@ torch::Tensor col_sum(torch::Tensor a) {
   auto f32 = a.options().dtype(torch::kFloat32);
   if (n % 8 == 0) {
     torch::Tensor out = torch::empty({n}, f32);
-    torch::Tensor scratch = torch::empty({2048, n}, f32);
+    torch::Tensor scratch = torch::empty({kPartRows, n}, f32);
     int gx = launch_col_sum_part(a.data_ptr(), scratch.data_ptr<float>(),
                                  (long)m, (int)n, cur_stream());
     launch_col_sum_sum2(scratch.data_ptr<float>(), gx, (int)n,
@@ -834,7 +668,7 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor gamma,
   if (c % 8 == 0) {
     sum = torch::empty({c}, f32);
     sumsq = torch::empty({c}, f32);
-    torch::Tensor scratch = torch::empty({2048, 2 * c}, f32);
+    torch::Tensor scratch = torch::empty({kPartRows, 2 * c}, f32);
     int gx = launch_bn_stats_part(x.data_ptr(), m, (int)c,
                                   scratch.data_ptr<float>(), s);
     launch_bn_stats_sum2(scratch.data_ptr<float>(), gx, (int)c,
@@ -919,7 +753,7 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor x, torch::Tensor dy,
   if (c % 8 == 0) {
     dgamma = torch::empty({c}, f32);
     dbeta = torch::empty({c}, f32);
-    torch::Tensor scratch = torch::empty({2048, 2 * c}, f32);
+    torch::Tensor scratch = torch::empty({kPartRows, 2 * c}, f32);
     int gx = launch_bn_bwd_reduce_part(x.data_ptr(), dy.data_ptr(), m,
                                        (int)c, mean.data_ptr<float>(),
                                        istd.data_ptr<float>(),
@@ -960,7 +794,7 @@ std::vector<torch::Tensor> bn_bwd_act(torch::Tensor x, torch::Tensor dy,
   auto s = cur_stream();
   torch::Tensor dgamma = torch::empty({c}, f32);
   torch::Tensor dbeta = torch::empty({c}, f32);
-  torch::Tensor scratch = torch::empty({2048, 2 * c}, f32);
+  torch::Tensor scratch = torch::empty({kPartRows, 2 * c}, f32);
   int gx = launch_bn_bwd_reduce_part(x.data_ptr(), dy.data_ptr(), m, (int)c,
                                      mean.data_ptr<float>(),
                                      istd.data_ptr<float>(),
@@ -971,7 +805,7 @@ std::vector<torch::Tensor> bn_bwd_act(torch::Tensor x, torch::Tensor dy,
   torch::Tensor bpart;
   float* bpart_p = nullptr;
   if (want_bias) {
-    bpart = torch::empty({2048, c}, f32);
+    bpart = torch::empty({kPartRows, c}, f32);
     bpart_p = bpart.data_ptr<float>();
   }
   int gx2 = launch_bn_bwd_apply_act(
@@ -1044,11 +878,7 @@ torch::Tensor gemm_tn_fp8(torch::Tensor Aq, torch::Tensor Bq,
   TORCH_CHECK(Aq.size(1) == Bq.size(1), "K mismatch");
   TORCH_CHECK(Aq.size(1) % 128 == 0, "fp8 K must be padded to 128");
   int64_t M = Aq.size(0), N = Bq.size(0), K = Aq.size(1);
-  const float* bias_p = nullptr;
-  if (bias.has_value() && bias->defined() && bias->numel() > 0) {
-    check_f32(*bias, "bias");
-    bias_p = bias->data_ptr<float>();
-  }
+  const float* bias_p = opt_f32_ptr(bias, "bias");
   torch::Tensor C = torch::empty({M, N},
                                  Aq.options().dtype(torch::kBFloat16));
   ConvGather dummy{};
@@ -1071,16 +901,12 @@ torch::Tensor conv_fwd_implicit_fp8(
   int64_t Kout = wq.size(0), kpad = wq.size(1);
   TORCH_CHECK(kpad % 128 == 0, "fp8 pack K must be padded to 128");
   int64_t M = Nb * Ho * Wo;
-  const float* bias_p = nullptr;
-  if (bias.has_value() && bias->defined() && bias->numel() > 0) {
-    check_f32(*bias, "bias");
-    bias_p = bias->data_ptr<float>();
-  }
+  const float* bias_p = opt_f32_ptr(bias, "bias");
   torch::Tensor y = torch::empty({M, Kout},
                                  xq.options().dtype(torch::kBFloat16));
-  ConvGather g = make_gather((int)Nb, (int)H, (int)W, (int)C, (int)Ho,
-                             (int)Wo, (int)R, (int)S, (int)stride, (int)pad,
-                             (int)mode);
+  ConvGather g = make_conv_gather((int)Nb, (int)H, (int)W, (int)C, (int)Ho,
+                                  (int)Wo, (int)R, (int)S, (int)stride,
+                                  (int)pad, (int)mode);
   launch_gemm_tn_fp8(xq.data_ptr(), wq.data_ptr(), y.data_ptr(), bias_p,
                      inv_qx.data_ptr<float>(), inv_qw.data_ptr<float>(),
                      (int)M, (int)Kout, (int)kpad, 0, kpad, (int)act,
@@ -1206,9 +1032,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("conv_dgrad_direct_p_eligible",
           [](int64_t H, int64_t W, int64_t C8, int64_t Ko8, int64_t ldw,
              int64_t R, int64_t S, int64_t stride, int64_t pad) {
-            return conv_dgrad_direct_p_eligible(
-                (int)H, (int)W, (int)C8, (int)Ko8, (long)ldw, (int)R,
-                (int)S, (int)stride, (int)pad);
+            return conv_dgrad_direct_plan((int)H, (int)W, (int)C8, (int)Ko8,
+                                          (long)ldw, (int)R, (int)S,
+                                          (int)stride, (int)pad, 1)
+                       .kind == 2 ? 1 : 0;
           },
           "nonzero when the persistent direct dgrad takes this geometry");
   mod.def("fused_adam", &fused_adam);

@@ -1052,14 +1052,9 @@ __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_core(
 // ---------------------------------------------------------------------------
 extern "C" {
 
-// 8-phase deep-pipelined 256x256 TN core (gemm8p.hip) — the default for
-// large bf16 TN shapes; this file's 128-tile kernels remain the fallback
+// The 8-phase deep-pipelined 256x256 TN core (gemm8p.hip) is the default
+// for large bf16 TN shapes; this file's 128-tile kernels remain the fallback
 // (fp32 out, bn_part fusion, small N/K/M).
-int gemm_tn_8p_eligible(int M, int N, int K);
-int launch_gemm_tn_8p(const void* A, const void* B, void* C,
-                      const float* bias, int M, int N, int K, long lda,
-                      long ldb, int act, float slope, int gather,
-                      ConvGather ga, const void* zp, hipStream_t s);
 
 // env-gated 256-row TN tile (see gemm_tn_core256). Opted in with
 // GDLJ_TN256=1; requires bf16 output, no bn_part, gather mode != 2,
@@ -1163,13 +1158,6 @@ int launch_gemm_tn(const void* A, const void* B, void* C_bf16, float* C_f32,
   return (int)grid.x;
 }
 
-// conv_direct.hip: LDS-image direct conv for the small-C forward family
-extern "C" int launch_conv_direct_smallc(const void*, const void*, void*,
-                                         const float*, const void*, int, int,
-                                         int, int, int, int, int, int, int,
-                                         int, int, int, int, float,
-                                         hipStream_t);
-
 static int direct_conv_enabled() {
   static int v = -1;
   if (v < 0) {
@@ -1180,7 +1168,8 @@ static int direct_conv_enabled() {
 }
 
 // implicit-GEMM conv forward / gathered-A TN: A is an NHWC image; M = the
-// number of patch positions; K = kpad (zero page covers k >= rsc).
+// number of patch positions; K = kpad (zero page covers k >= rsc).  The
+// small-C forward family goes to the LDS-image direct conv (conv_direct.hip).
 int launch_gemm_tn_gather(const void* img, const void* B, void* C_bf16,
                           const float* bias, int M, int N, int K, long ldb,
                           int act, float slope, ConvGather ga,

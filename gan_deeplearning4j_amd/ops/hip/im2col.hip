@@ -11,14 +11,6 @@
 
 #include "common.h"
 
-struct ConvGeom {
-  int N, H, W, C;       // image dims (the im2col SOURCE / col2im TARGET)
-  int Ho, Wo;           // patch-grid dims
-  int R, S;             // kernel
-  int stride, pad;
-  int kpad;             // padded K = round_up(R*S*C, 64)
-};
-
 __global__ void im2col_nhwc(const unsigned short* __restrict__ in,
                             unsigned short* __restrict__ col, ConvGeom g) {
   // one thread per col element (vectorized x2 over c when C % 2 == 0 is a
@@ -338,7 +330,7 @@ int launch_col2im_stats(const void* dcol, void* din, ConvGeom g,
   int lanes = 256 / groups;
   long rows = (long)g.N * g.H * g.W;
   long chunks = (rows + lanes - 1) / lanes;
-  dim3 grid((unsigned)min((long)2048, max((long)1, chunks)),
+  dim3 grid((unsigned)min((long)kPartRows, max((long)1, chunks)),
             (unsigned)ceil_div(c8, 32));
   if (g.stride == 2)
     hipLaunchKernelGGL((col2im_stats_v8<2>), grid, dim3(256), 0, s,
@@ -366,8 +358,8 @@ int launch_col2im_dact(const void* dcol, void* din, ConvGeom g,
   long chunks = (rows + lanes - 1) / lanes;
   // col2im gathers R*S taps per pixel: it needs a near-full grid (a
   // 256-block cap measured 4x slower at DCGAN-64 dgrad sizes); partials
-  // rows scale with grid.x (buffer sized 2048 in the binding)
-  dim3 grid((unsigned)min((long)2048, max((long)1, chunks)),
+  // rows scale with grid.x (the binding's buffer has kPartRows)
+  dim3 grid((unsigned)min((long)kPartRows, max((long)1, chunks)),
             (unsigned)ceil_div(c8, 32));
   if (g.stride == 2)
     hipLaunchKernelGGL((col2im_dact_v8<2>), grid, dim3(256), 0, s,

@@ -4,12 +4,6 @@
 
 #include "common.h"
 
-struct PoolGeom {
-  int N, H, W, C;   // input dims
-  int Ho, Wo;       // output dims
-  int k, stride;    // kernel, stride (square)
-};
-
 __global__ void maxpool_fwd_nhwc(const unsigned short* __restrict__ in,
                                  unsigned short* __restrict__ out,
                                  unsigned char* __restrict__ argmax,

@@ -34,13 +34,17 @@ HIP_FLAGS = [
 ]
 
 
+HIP_HEADERS = sorted(HIP_DIR.glob("*.h"))
+
+
 def compile_hip_objects() -> list[str]:
     OBJ_DIR.mkdir(parents=True, exist_ok=True)
     objs = []
     for src in HIP_SOURCES:
         obj = OBJ_DIR / (src.stem + ".o")
-        if not obj.exists() or obj.stat().st_mtime < src.stat().st_mtime or \
-                obj.stat().st_mtime < (HIP_DIR / "common.h").stat().st_mtime:
+        # stale when older than its source or than ANY header in ops/hip/
+        if not obj.exists() or obj.stat().st_mtime < max(
+                f.stat().st_mtime for f in [src, *HIP_HEADERS]):
             cmd = [HIPCC, *HIP_FLAGS, str(src), "-o", str(obj)]
             print("[hipcc]", " ".join(cmd))
             subprocess.run(cmd, check=True)
@@ -52,6 +56,7 @@ ext = cpp_extension.CUDAExtension(
     name="gan_deeplearning4j_amd._C",
     sources=[str(HIP_DIR / "ext.cpp"), str(HIP_DIR / "csv_loader.cpp")],
     extra_objects=compile_hip_objects(),
+    depends=[str(h) for h in HIP_HEADERS],
     extra_compile_args={"cxx": ["-O2"], "nvcc": ["-O2"]},
 )
 
