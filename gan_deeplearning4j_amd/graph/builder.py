@@ -142,13 +142,16 @@ class ComputationGraph(nn.Module):
         SOLE consumer is a BatchNorm over the same feature axis (no
         preprocessor in between):
 
-        - backward act-fusion (always on; kill switch GDLJ_NO_ACT_FUSE):
-          BN's backward kernel applies the producer's activation backward
-          and reduces the producer's bias gradient in the same pass,
-          removing the standalone act_bwd_bias tensor streams.
+        - backward act-fusion (always on; the kill switch is read per call
+          in ops/gpu_ops.py): BN's backward kernel applies the producer's
+          activation backward and reduces the producer's bias gradient in
+          the same pass, removing the standalone act_bwd_bias tensor
+          streams.
         - statistics fusion (opt-in via GDLJ_BN_FUSE, measured ~neutral-
           to-negative on DCGAN-64): the producer's GPU epilogue also emits
-          the BN batch statistics, skipping BN's own stats pass."""
+          the BN batch statistics, skipping BN's own stats pass.
+
+        Both gates are in the "Environment gates" table of docs/KERNELS.md."""
         import os
 
         stats_fuse = os.environ.get("GDLJ_BN_FUSE", "0") == "1"

@@ -13,10 +13,14 @@ padded with one small copy.
 
 Every Function here raises if the _C extension is missing — on a GPU box
 the HIP path is the only path (no silent eager fallback).
+
+Which extension entry points a call reaches is pinned, without a GPU, by
+tests/test_gpu_ops_routing.py.
 """
 
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -27,34 +31,112 @@ ACT_CODES = {"identity": 0, None: 0, "tanh": 1, "sigmoid": 2, "lrelu": 3,
              "relu": 4}
 
 
-def _rup64(k: int) -> int:
-    return (k + 63) // 64 * 64
+# ===================================================================== gates
+# Every GDLJ_* switch this module routes on, one predicate each. Defaults,
+# when each is read and the measurement behind it: docs/KERNELS.md,
+# "Environment gates".
+def _gate(name: str) -> Optional[str]:
+    return os.environ.get(name)
+
+
+# Strided dgrad/convT-fwd algorithm choice: parity-decomposed gathered
+# GEMMs vs dcol+col2im. Measured on DCGAN-64: dcol wins by ~4% (the
+# parity gather re-reads the source once per tap, so traffic is a wash
+# and the 4 launches add overhead); parity kept selectable for other
+# shapes. Read at import; the routes read the attribute per call.
+PARITY_STRIDED = _gate("GDLJ_PARITY") == "1"
+
+# FP8 conv-forward mode (BASELINE config 4: DCGAN-128 fp8 MFMA path).
+# When enabled, conv forwards with C % 16 == 0 quantize activations and
+# weights to e4m3 (per-tensor dynamic scale) and run the fp8 MFMA implicit
+# GEMM; backward stays bf16.
+FP8_CONV = False
+
+
+def set_fp8_conv(enabled: bool) -> None:
+    global FP8_CONV
+    FP8_CONV = bool(enabled)
+
+
+def _dgrad_direct_on() -> bool:
+    """Fused direct strided dgrad / convT forward (conv_dgrad_direct.hip),
+    default on."""
+    return _gate("GDLJ_DGRAD_DIRECT") != "0"
+
+
+def _act_fuse_on() -> bool:
+    """Producer act-backward fusion into the consumer's BN backward or
+    col2im; GDLJ_NO_ACT_FUSE=1 is the kill switch."""
+    return _gate("GDLJ_NO_ACT_FUSE") != "1"
+
+
+def _smallc_col_on() -> bool:
+    """Explicit im2col for C8 <= 16 conv forwards. MEASURED NEGATIVE,
+    opt-in only (dcgan64 117.0k -> 114.4k, dcgan28 791k -> 765k): the
+    hypothesis was that small-C gathers are TA-address-bound (a gathered
+    16B chunk spans 2+ taps -> 64 scattered addresses per glds) and an
+    explicit coalesced im2col + plain-TN GEMM would win; the col round
+    trip costs more than the scattered addressing does."""
+    return _gate("GDLJ_SMALLC_COL") == "1"
+
+
+# fp8 backward (dgrad family) is implemented and numerics-tested but OFF
+# by default (GDLJ_FP8_BWD=1 opts in): measured on DCGAN-128 at batches
+# 512-2048, fp8 dgrad is 4-6% SLOWER end-to-end than bf16 dgrad — the
+# dgrad GEMMs are K-thin (K = Cout <= 1024) and memory-bound on the
+# C-write/A-read stream, so halving the A bytes saves less than the
+# extra quantize pass (a full dy read + fp8 write) costs
+# (profiles/fp8_bwd_ab.md). fp8 pays where MFMA rate is the bound: the
+# K-deep forward gathers (on by default). wgrad stays bf16: the NT
+# contraction reads both operands k(=np)-major, and glds cannot build
+# the transposed fp8 LDS image (lane-linear dest; no tr16-style
+# transpose read exists for 8-bit fragments at the 16x16x128 layout).
+def _fp8_bwd_on() -> bool:
+    return FP8_CONV and _gate("GDLJ_FP8_BWD") == "1"
+
+
+def _fp8_delayed_on() -> bool:
+    """Delayed fp8 scaling; GDLJ_FP8_DELAYED=0 falls back to exact
+    per-call scaling."""
+    return _gate("GDLJ_FP8_DELAYED") != "0"
+
+
+# GDLJ_FP8_CONVT has three states. Unset: only the stride-1 convT forward
+# runs fp8 (K = rsc, deep — fp8 pays). "0": no convT runs fp8. "1": the
+# strided convT also takes the fp8 dcol GEMM, and for that skips the
+# direct kernel (K = Cin <= 1024, thin and memory-bound: measured -2%
+# end-to-end at dcgan128 b2048, profiles/fp8_bwd_ab.md).
+def _fp8_convt_s1_on() -> bool:
+    return FP8_CONV and _gate("GDLJ_FP8_CONVT") != "0"
+
+
+def _fp8_convt_strided_on() -> bool:
+    return FP8_CONV and _gate("GDLJ_FP8_CONVT") == "1"
+
+
+# =================================================================== helpers
+def _rup(x: int, m: int) -> int:
+    return (x + m - 1) // m * m
 
 
 def _bf(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.bfloat16).contiguous()
 
 
+def _pad_last(t: torch.Tensor, m: int) -> torch.Tensor:
+    """Zero-pad the last dim to a multiple of m (contiguous result)."""
+    k = t.shape[-1]
+    kp = _rup(k, m)
+    if kp == k:
+        return t.contiguous()
+    out = t.new_zeros(*t.shape[:-1], kp)
+    out[..., :k] = t
+    return out
+
+
 def _pad_k(t: torch.Tensor) -> torch.Tensor:
-    """Zero-pad the last dim of a 2D tensor to a multiple of 64."""
-    k = t.shape[-1]
-    kp = _rup64(k)
-    if kp == k:
-        return t.contiguous()
-    out = t.new_zeros(*t.shape[:-1], kp)
-    out[..., :k] = t
-    return out
-
-
-def _pad8(t: torch.Tensor) -> torch.Tensor:
-    """Zero-pad the last dim to a multiple of 8 (gemm_nt row alignment)."""
-    k = t.shape[-1]
-    kp = (k + 7) // 8 * 8
-    if kp == k:
-        return t.contiguous()
-    out = t.new_zeros(*t.shape[:-1], kp)
-    out[..., :k] = t
-    return out
+    """Zero-pad the contraction (last) dim to the 64-deep MFMA tile."""
+    return _pad_last(t, 64)
 
 
 def _nhwc(x: torch.Tensor) -> torch.Tensor:
@@ -146,45 +228,19 @@ def take_chan_pad(t: torch.Tensor, c8: int):
         return p
     return None
 
-# Strided dgrad/convT-fwd algorithm choice: parity-decomposed gathered
-# GEMMs vs dcol+col2im. Measured on DCGAN-64: dcol wins by ~4% (the
-# parity gather re-reads the source once per tap, so traffic is a wash
-# and the 4 launches add overhead); parity kept selectable for other
-# shapes.
-import os
 
-PARITY_STRIDED = os.environ.get("GDLJ_PARITY", "0") == "1"
-
-
-def _dgrad_direct_on() -> bool:
-    """Fused direct strided dgrad (conv_dgrad_direct.hip), default on."""
-    return os.environ.get("GDLJ_DGRAD_DIRECT", "1") != "0"
-
-# FP8 conv-forward mode (BASELINE config 4: DCGAN-128 fp8 MFMA path).
-# When enabled, conv forwards with C % 16 == 0 quantize activations and
-# weights to e4m3 (per-tensor dynamic scale) and run the fp8 MFMA implicit
-# GEMM; backward stays bf16.
-FP8_CONV = False
-
-
-def set_fp8_conv(enabled: bool) -> None:
-    global FP8_CONV
-    FP8_CONV = bool(enabled)
-
-
-# fp8 backward (dgrad family) is implemented and numerics-tested but OFF
-# by default (GDLJ_FP8_BWD=1 opts in): measured on DCGAN-128 at batches
-# 512-2048, fp8 dgrad is 4-6% SLOWER end-to-end than bf16 dgrad — the
-# dgrad GEMMs are K-thin (K = Cout <= 1024) and memory-bound on the
-# C-write/A-read stream, so halving the A bytes saves less than the
-# extra quantize pass (a full dy read + fp8 write) costs
-# (profiles/fp8_bwd_ab.md). fp8 pays where MFMA rate is the bound: the
-# K-deep forward gathers (on by default). wgrad stays bf16: the NT
-# contraction reads both operands k(=np)-major, and glds cannot build
-# the transposed fp8 LDS image (lane-linear dest; no tr16-style
-# transpose read exists for 8-bit fragments at the 16x16x128 layout).
-def _fp8_bwd_on() -> bool:
-    return FP8_CONV and os.environ.get("GDLJ_FP8_BWD") == "1"
+def _trim_channels(th: torch.Tensor, c: int, as_view: bool) -> torch.Tensor:
+    """NHWC [..., c8] buffer -> its first c channels (th itself when
+    c8 == c). as_view: a [..., :c] view, with the padded buffer deposited
+    for the next conv to take whole — the caller vouches that the pad
+    channels are exact zeros; otherwise one contiguous trim-copy."""
+    if th.shape[-1] != c:
+        if as_view:
+            padded, th = th, th[..., :c]
+            deposit_chan_pad(th, padded)
+        else:
+            th = th[..., :c].contiguous()
+    return th
 
 
 def _fp8_state(w: torch.Tensor, role: str, device) -> list:
@@ -207,10 +263,9 @@ def _fp8_state(w: torch.Tensor, role: str, device) -> list:
 
 def _quant_delayed(x: torch.Tensor, w: torch.Tensor, role: str):
     """Quantize x to e4m3 with the previous step's scale (fused amax
-    accumulation; exact two-pass on first use). Returns (q, inv_scale).
-    GDLJ_FP8_DELAYED=0 falls back to exact per-call scaling."""
+    accumulation; exact two-pass on first use). Returns (q, inv_scale)."""
     ext = hip_ext()
-    if os.environ.get("GDLJ_FP8_DELAYED") == "0":
+    if not _fp8_delayed_on():
         q, _, inv = ext.fp8_quantize(x.contiguous())
         return q, inv
     st = _fp8_state(w, role, x.device)
@@ -219,26 +274,13 @@ def _quant_delayed(x: torch.Tensor, w: torch.Tensor, role: str):
     return y, st[1]
 
 
-def _pad_k128(t: torch.Tensor) -> torch.Tensor:
-    k = t.shape[1]
-    if k % 128:
-        t = torch.nn.functional.pad(t, (0, 128 - k % 128))
-    return t
-
-
-def _zp8(device) -> torch.Tensor:
-    key = "fp8:" + str(device)
+def _zero_page(device, dtype=torch.bfloat16) -> torch.Tensor:
+    """32 zero bytes, viewed as dtype, for gathered global_load_lds
+    (OOB/pad chunks redirect there). One per (device, dtype)."""
+    key = (device, dtype)
     if key not in _zero_pages:
-        _zero_pages[key] = torch.zeros(32, dtype=torch.uint8, device=device)
-    return _zero_pages[key]
-
-
-def _zp(device) -> torch.Tensor:
-    """16B zero page for gathered global_load_lds (OOB/pad redirect)."""
-    key = str(device)
-    if key not in _zero_pages:
-        _zero_pages[key] = torch.zeros(16, dtype=torch.bfloat16,
-                                       device=device)
+        _zero_pages[key] = torch.zeros(32, dtype=torch.uint8,
+                                       device=device).view(dtype)
     return _zero_pages[key]
 
 
@@ -267,6 +309,43 @@ def _packed(w: torch.Tensor, key: str, builder):
     return d[key]
 
 
+def _fp8_pack(owner: torch.Tensor, key: str, pack: torch.Tensor):
+    """(q, scale, inv_scale) e4m3 image of a bf16 weight pack, cached on
+    owner. The double-rate fp8 MFMA consumes K in 128-deep tiles."""
+    return _packed(owner, key, lambda: tuple(
+        hip_ext().fp8_quantize(_pad_last(pack, 128))))
+
+
+def _bias_f32(b):
+    return (None if b is None else
+            _packed(b, "f32", lambda: b.detach().float().contiguous()))
+
+
+def _act_bwd(ctx, dy, y, n: int, c: int, fused, want_bias: bool):
+    """Gradient at the producer's pre-activation, n channels wide of which
+    the first c are real: (dpre [M, n], bias grad [c] or None when it is
+    still to be reduced). `fused` is what a consumer left in the act-fusion
+    side channel; when it matches, dy already IS dpre."""
+    ext = hip_ext()
+    dy2d = dy.reshape(-1, n)
+    db = None
+    if fused is not None and fused[0] == ctx.act and fused[1] == n:
+        # the consumer already applied act backward + bias reduction
+        dpre = dy2d
+        if want_bias and fused[2] is not None:
+            db = fused[2].to(ctx.dtypes[2])
+    elif ctx.act and want_bias and n % 8 == 0:
+        dpre, db_f = ext.act_bwd_bias(dy2d, y.reshape(-1, n).contiguous(),
+                                      ctx.act, ctx.slope)
+        db = db_f[:c].to(ctx.dtypes[2])
+    elif ctx.act:
+        dpre = ext.act_bwd(dy2d, y.reshape(-1, n).contiguous(), ctx.act,
+                           ctx.slope)
+    else:
+        dpre = dy2d
+    return dpre, db
+
+
 # ===================================================================== linear
 class _Linear(torch.autograd.Function):
     @staticmethod
@@ -274,8 +353,7 @@ class _Linear(torch.autograd.Function):
         ext = hip_ext()
         xp = _pad_k(_bf(x))
         wp = _packed(w, "wp", lambda: _pad_k(_bf(w.detach())))
-        bias = (_packed(b, "f32", lambda: b.detach().float().contiguous())
-                if b is not None else None)
+        bias = _bias_f32(b)
         if emit_stats and w.shape[0] % 8 == 0:
             y, ssum, ssq = ext.gemm_tn_stats(xp, wp, bias, act, slope)
             deposit_bn_stats(y, (ssum, ssq))
@@ -294,38 +372,26 @@ class _Linear(torch.autograd.Function):
         xp, wp, y = ctx.saved_tensors
         fused = take_act_fused(dy)
         dy = _bf(dy)
-        dx = dw = db = None
+        dx = dw = None
         want_bias = ctx.has_bias and ctx.needs_input_grad[2]
-        if fused is not None and fused[0] == ctx.act and \
-                fused[1] == dy.shape[1]:
-            # consumer BN already applied act backward + bias reduction
-            dpre = dy
-            if want_bias and fused[2] is not None:
-                db = fused[2].to(ctx.dtypes[2])
-        elif ctx.act and want_bias and dy.shape[1] % 8 == 0:
-            dpre, db_f = ext.act_bwd_bias(dy, y, ctx.act, ctx.slope)
-            db = db_f.to(ctx.dtypes[2])
-        else:
-            dpre = ext.act_bwd(dy, y, ctx.act, ctx.slope) if ctx.act else dy
+        nout = dy.shape[1]
+        dpre, db = _act_bwd(ctx, dy, y, nout, nout, fused, want_bias)
         if ctx.needs_input_grad[0]:
             # dgrad: dx = dpre @ w ;  B = w^T padded over nout
             nin = ctx.nin
             wt = _packed(wp, "wt",
                          lambda: _pad_k(wp[:, :nin].t().contiguous()))
-            dprep = _pad_k(dpre)
-            dx = ext.gemm_tn(dprep, wt, None, 0, 0.0, False)
+            dx = ext.gemm_tn(_pad_k(dpre), wt, None, 0, 0.0, False)
             if dx.shape[1] != ctx.nin:
                 dx = dx[:, : ctx.nin].contiguous()
         if ctx.needs_input_grad[1]:
             # wgrad: dw = dpre^T-contracted-with-x (rows = batch); padded
             # x cols are zero so the sliced grad region is exact
-            nout = wp.shape[0]
             kchunks = (xp.shape[0] + 63) // 64
             sk = _splitk_for((nout + 127) // 128, (ctx.nin + 127) // 128, kchunks)
-            dpre8 = _pad8(dpre)
-            dw = ext.gemm_nt(dpre8, xp, sk, _zp(xp.device))
+            dw = ext.gemm_nt(_pad_last(dpre, 8), xp, sk, _zero_page(xp.device))
             dw = dw[: nout, : ctx.nin].contiguous().to(ctx.dtypes[1])
-        if ctx.has_bias and ctx.needs_input_grad[2] and db is None:
+        if want_bias and db is None:
             db = ext.col_sum(dpre).to(ctx.dtypes[2])
         if dx is not None:
             dx = dx.to(ctx.dtypes[0])
@@ -350,12 +416,131 @@ def _pad_channels(xh: torch.Tensor, c8: int) -> torch.Tensor:
     new_empty + two slice writes beats new_zeros + copy (the full-buffer
     zero fill re-wrote the data region for nothing)."""
     n, h, w, c = xh.shape
-    if c == c8:
-        return xh
-    out = xh.new_empty(n, h, w, c8)
-    out[..., :c] = xh
-    out[..., c:] = 0
+    out = xh
+    if c != c8:
+        out = xh.new_empty(n, h, w, c8)
+        out[..., :c] = xh
+        out[..., c:] = 0
     return out
+
+
+def _weight_taps(w: torch.Tensor, perm, c8: int) -> torch.Tensor:
+    """Weight permuted to [out, R, S, c] in bf16, c zero-padded to c8."""
+    wc = _bf(w.detach().permute(*perm))
+    o, r, s, c = wc.shape
+    return _pad_channels(wc.reshape(o * r * s, 1, 1, c),
+                         c8).reshape(o, r, s, c8)
+
+
+def _parity_class_packs(wc: torch.Tensor, stride: int, pad: int) -> list:
+    """[out, R, S, c] taps -> one K-padded [out, taps_q * c] pack per
+    output parity class (qh-major), each over the class's valid taps."""
+    packs = []
+    for qh in range(stride):
+        for qw in range(stride):
+            prh = (qh + pad) % stride
+            prw = (qw + pad) % stride
+            sub = wc[:, prh::stride, prw::stride, :]
+            packs.append(_pad_k(sub.reshape(wc.shape[0], -1).contiguous()))
+    return packs
+
+
+def _conv_wgrad(ctx, dpre8, xh):
+    """dw as one implicit gathered-B NT GEMM (rows = N*Ho*Wo)."""
+    N, C, H, W, Kout, R, S, Ho, Wo, stride, pad, kpad, C8 = ctx.geom
+    npq, Ko8 = dpre8.shape
+    sk = _splitk_for((Ko8 + 127) // 128, (kpad + 127) // 128,
+                     (npq + 63) // 64)
+    dw = hip_ext().gemm_nt_implicit(
+        dpre8, xh, 2, Ko8, kpad, npq,
+        _dims(N, H, W, C8, Ho, Wo, R, S, stride, pad), sk,
+        _zero_page(xh.device))
+    return (dw[:Kout, :R * S * C8].reshape(Kout, R, S, C8)[..., :C]
+            .permute(0, 3, 1, 2).contiguous().to(ctx.dtypes[1]))
+
+
+def _conv_dgrad_s1(ctx, dpre8):
+    """Stride 1: dgrad as ONE transposed-gather GEMM (no dcol/col2im;
+    every tap valid at stride 1)."""
+    ext = hip_ext()
+    N, C, H, W, Kout, R, S, Ho, Wo, stride, pad, kpad, C8 = ctx.geom
+    w = ctx.wref
+    Ko8 = dpre8.shape[1]
+    wd = _packed(w, "dgrad_w", lambda: _pad_k(
+        _weight_taps(w, (1, 2, 3, 0), Ko8).reshape(C, R * S * Ko8)))
+    dpre_img = dpre8.view(N, Ho, Wo, Ko8)
+    if _fp8_bwd_on() and Ko8 % 16 == 0:
+        wdq, _, iwd = _fp8_pack(w, "dgrad_w_fp8", wd)
+        dq, idy = _quant_delayed(dpre_img, w, "dy")
+        dx2d = ext.conv_fwd_implicit_fp8(
+            dq, wdq, None, idy, iwd, _zero_page(dpre8.device, torch.uint8),
+            N, Ho, Wo, Ko8, H, W, R, S, stride, pad, 0, 0.0, 1)
+    else:
+        dx2d = ext.conv_fwd_implicit(
+            dpre_img, wd, None, _zero_page(dpre8.device), N, Ho, Wo, Ko8, H,
+            W, R, S, stride, pad, 0, 0.0, 1, 0)[0]
+    return _as_nchw_view(dx2d.view(N, H, W, C)).to(ctx.dtypes[0])
+
+
+def _conv_dgrad_parity(ctx, dpre8):
+    """Strided, GDLJ_PARITY: parity-decomposed gather (each output parity
+    class is a dense GEMM over its valid taps only)."""
+    N, C, H, W, Kout, R, S, Ho, Wo, stride, pad, kpad, C8 = ctx.geom
+    w = ctx.wref
+    Ko8 = dpre8.shape[1]
+    wd_cls = _packed(w, "dgrad_wcls", lambda: _parity_class_packs(
+        _weight_taps(w, (1, 2, 3, 0), Ko8), stride, pad))
+    dx2d = hip_ext().conv_parity_implicit(
+        dpre8.view(N, Ho, Wo, Ko8), wd_cls, None, _zero_page(dpre8.device),
+        N, Ho, Wo, Ko8, H, W, C, R, S, stride, pad, 0, 0.0)
+    return _as_nchw_view(dx2d.view(N, H, W, C)).to(ctx.dtypes[0])
+
+
+def _conv_dgrad_strided(ctx, dpre, dpre8, xh, wp):
+    """Strided default: the fused direct kernel (conv_dgrad_direct.hip)
+    when the geometry qualifies, else dcol GEMM + col2im gather. With
+    prev_act the producer's act backward folds into either (xh IS the
+    producer's activation output) along with its bias-grad column sums;
+    both go to the producer through the side channel so it skips its own
+    pass."""
+    ext = hip_ext()
+    N, C, H, W, Kout, R, S, Ho, Wo, stride, pad, kpad, C8 = ctx.geom
+    rsc8 = R * S * C8
+    wt = _packed(wp, "wt", lambda: _pad_k(
+        wp[:, :rsc8].t().contiguous()))   # [rsc8, kout_pad]
+    pact = ctx.prev_act if C8 == C and _act_fuse_on() else None
+    p_code, p_slope, p_bias = pact if pact is not None else (0, 0.0, None)
+    fp8 = _fp8_bwd_on()
+    res = None
+    if not fp8 and _dgrad_direct_on():
+        res = ext.conv_dgrad_direct(
+            dpre8, wt, xh if pact is not None else None,
+            _zero_page(dpre.device), N, H, W, C8, Ho, Wo, R, S, stride, pad,
+            p_code, p_slope, p_bias is not False and p_bias is not None)
+    if res:
+        dxh, pdb = res[0], res[1] if len(res) > 1 else None
+    else:
+        if fp8:
+            wtq, _, iwt = _fp8_pack(wp, "wt_fp8", wt)
+            dq, idy = _quant_delayed(_pad_last(dpre, 128), ctx.wref, "dy")
+            dcol = ext.gemm_tn_fp8(dq, wtq, idy, iwt, None, 0, 0.0)
+        else:
+            dcol = ext.gemm_tn(_pad_k(dpre), wt, None, 0, 0.0, False)
+        if pact is not None:
+            dxh, pdb = ext.col2im_dact(
+                dcol, N, H, W, C8, Ho, Wo, R, S, stride, pad, rsc8, xh,
+                p_code, p_slope, p_bias)
+            pdb = pdb if p_bias else None
+        else:
+            dxh, pdb = ext.col2im(dcol, N, H, W, C8, Ho, Wo, R, S, stride,
+                                  pad, rsc8, None, 0, 0.0), None
+    # at the channel-pad boundary the padded dx (pad lanes: zero weight
+    # rows) passes through to a convT producer when no cast intervenes
+    dx = _as_nchw_view(_trim_channels(
+        dxh, C, dxh.dtype == ctx.dtypes[0])).to(ctx.dtypes[0])
+    if pact is not None:
+        deposit_act_fused(dx, (p_code, C, pdb))
+    return dx
 
 
 class _Conv2d(torch.autograd.Function):
@@ -367,46 +552,22 @@ class _Conv2d(torch.autograd.Function):
         Kout, _, R, S = w.shape
         Ho, Wo = _conv_out(H, R, stride, pad), _conv_out(W, S, stride, pad)
         # channel dim padded to 8 so every conv runs the implicit path
-        C8 = (C + 7) // 8 * 8
+        C8 = _rup(C, 8)
         xh = take_chan_pad(x, C8)
         if xh is None:
             xh = _pad_channels(_nhwc(x), C8)
-        kpad = _rup64(R * S * C8)
-
-        def build_wp():
-            wc = _bf(w.detach().permute(0, 2, 3, 1))     # [Kout,R,S,C]
-            wc = _pad_channels(wc.reshape(Kout * R * S, 1, 1, C),
-                               C8).reshape(Kout, R * S * C8)
-            return _pad_k(wc)
-
-        wp = _packed(w, "conv_wp", build_wp)
-        bias = (_packed(b, "f32", lambda: b.detach().float().contiguous())
-                if b is not None else None)
+        kpad = _rup(R * S * C8, 64)
+        wp = _packed(w, "conv_wp", lambda: _pad_k(
+            _weight_taps(w, (0, 2, 3, 1), C8).reshape(Kout, R * S * C8)))
+        bias = _bias_f32(b)
         stats = None
         if FP8_CONV and C8 % 16 == 0:
             xq, ix = _quant_delayed(xh, w, "x")
-
-            def build_fp8_pack():
-                # the double-rate fp8 MFMA consumes K in 128-deep tiles
-                wpk = wp
-                if wpk.shape[1] % 128:
-                    wpk = torch.nn.functional.pad(
-                        wpk, (0, 128 - wpk.shape[1] % 128))
-                return tuple(ext.fp8_quantize(wpk))
-
-            wq, _, iw = _packed(w, "fp8", build_fp8_pack)
-            zp8 = _packed(wp, "zp8", lambda: torch.zeros(
-                32, dtype=torch.uint8, device=x.device))
-            y2d = ext.conv_fwd_implicit_fp8(xq, wq, bias, ix, iw, zp8, N, H,
-                                            W, C8, Ho, Wo, R, S, stride, pad,
-                                            act, slope, 0)
-        elif C8 <= 16 and os.environ.get("GDLJ_SMALLC_COL") == "1":
-            # MEASURED NEGATIVE, opt-in only (dcgan64 117.0k -> 114.4k,
-            # dcgan28 791k -> 765k): the hypothesis was that small-C
-            # gathers are TA-address-bound (a gathered 16B chunk spans
-            # 2+ taps -> 64 scattered addresses per glds) and an explicit
-            # coalesced im2col + plain-TN GEMM would win; the col round
-            # trip costs more than the scattered addressing does.
+            wq, _, iw = _fp8_pack(w, "fp8", wp)
+            y2d = ext.conv_fwd_implicit_fp8(
+                xq, wq, bias, ix, iw, _zero_page(x.device, torch.uint8), N,
+                H, W, C8, Ho, Wo, R, S, stride, pad, act, slope, 0)
+        elif C8 <= 16 and _smallc_col_on():
             col = ext.im2col(xh, N, H, W, C8, Ho, Wo, R, S, stride, pad,
                              kpad)
             if emit_stats and Kout % 8 == 0:
@@ -418,9 +579,9 @@ class _Conv2d(torch.autograd.Function):
         else:
             # implicit GEMM: im2col gather fused into the MFMA staging
             # (optionally also emitting the consumer BN's batch statistics)
-            res = ext.conv_fwd_implicit(xh, wp, bias, _zp(x.device), N, H, W,
-                                        C8, Ho, Wo, R, S, stride, pad, act,
-                                        slope, 0, 1 if emit_stats else 0)
+            res = ext.conv_fwd_implicit(
+                xh, wp, bias, _zero_page(x.device), N, H, W, C8, Ho, Wo, R,
+                S, stride, pad, act, slope, 0, 1 if emit_stats else 0)
             y2d = res[0]
             if len(res) == 3:
                 stats = (res[1], res[2])
@@ -438,167 +599,25 @@ class _Conv2d(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        ext = hip_ext()
         xh, wp, y2d = ctx.saved_tensors
-        N, C, H, W, Kout, R, S, Ho, Wo, stride, pad, kpad, C8 = ctx.geom
+        Kout, stride = ctx.geom[4], ctx.geom[9]
+        want_bias = ctx.has_bias and ctx.needs_input_grad[2]
         fused = take_act_fused(dy)
         dy2d = _bf(dy.permute(0, 2, 3, 1)).reshape(-1, Kout)
-        dx = dw = db = None
-        want_bias = ctx.has_bias and ctx.needs_input_grad[2]
-        if fused is not None and fused[0] == ctx.act and fused[1] == Kout:
-            # consumer BN already applied act backward + bias reduction
-            dpre = dy2d
-            if want_bias and fused[2] is not None:
-                db = fused[2].to(ctx.dtypes[2])
-        elif ctx.act and want_bias and Kout % 8 == 0:
-            dpre, db_f = ext.act_bwd_bias(dy2d, y2d, ctx.act, ctx.slope)
-            db = db_f.to(ctx.dtypes[2])
-        else:
-            dpre = (ext.act_bwd(dy2d, y2d, ctx.act, ctx.slope)
-                    if ctx.act else dy2d)
-        Ko8 = (Kout + 7) // 8 * 8
-        dpre8 = _pad8(dpre) if Ko8 != Kout else dpre
+        dpre, db = _act_bwd(ctx, dy2d, y2d, Kout, Kout, fused, want_bias)
+        dpre8 = _pad_last(dpre, 8)
+        dx = dw = None
         if ctx.needs_input_grad[1]:
-            # wgrad: implicit gathered-B NT (rows = N*Ho*Wo)
-            npq = dpre.shape[0]
-            sk = _splitk_for((Ko8 + 127) // 128, (kpad + 127) // 128,
-                             (npq + 63) // 64)
-            dw = ext.gemm_nt_implicit(
-                dpre8, xh, 2, Ko8, kpad, npq,
-                _dims(N, H, W, C8, Ho, Wo, R, S, stride, pad), sk,
-                _zp(xh.device))
-            dw = (dw[:Kout, :R * S * C8].reshape(Kout, R, S, C8)[..., :C]
-                  .permute(0, 3, 1, 2).contiguous().to(ctx.dtypes[1]))
+            dw = _conv_wgrad(ctx, dpre8, xh)
         if ctx.needs_input_grad[0]:
-            w = ctx.wref
             if stride == 1:
-                # dgrad as ONE transposed-gather GEMM (no dcol/col2im;
-                # every tap valid at stride 1)
-                def build_wd():
-                    wc = _bf(w.detach().permute(1, 2, 3, 0))  # [C,R,S,Kout]
-                    wc = _pad_channels(wc.reshape(C * R * S, 1, 1, Kout),
-                                       Ko8).reshape(C, R * S * Ko8)
-                    return _pad_k(wc)
-
-                wd = _packed(w, "dgrad_w", build_wd)
-                dpre_img = dpre8.view(N, Ho, Wo, Ko8)
-                if _fp8_bwd_on() and Ko8 % 16 == 0:
-                    wdq, _, iwd = _packed(w, "dgrad_w_fp8", lambda: tuple(
-                        ext.fp8_quantize(_pad_k128(wd))))
-                    dq, idy = _quant_delayed(dpre_img, w, "dy")
-                    dx2d = ext.conv_fwd_implicit_fp8(
-                        dq, wdq, None, idy, iwd, _zp8(dpre.device), N, Ho,
-                        Wo, Ko8, H, W, R, S, stride, pad, 0, 0.0, 1)
-                else:
-                    dx2d = ext.conv_fwd_implicit(
-                        dpre_img, wd, None, _zp(dpre.device), N, Ho, Wo,
-                        Ko8, H, W, R, S, stride, pad, 0, 0.0, 1, 0)[0]
-                dx = _as_nchw_view(dx2d.view(N, H, W, C)).to(ctx.dtypes[0])
+                dx = _conv_dgrad_s1(ctx, dpre8)
             elif PARITY_STRIDED:
-                # strided: parity-decomposed gather (each output parity
-                # class is a dense GEMM over its valid taps only)
-                def build_wd_cls():
-                    wc = _bf(w.detach().permute(1, 2, 3, 0))  # [C,R,S,Kout]
-                    wc = _pad_channels(
-                        wc.reshape(C * R * S, 1, 1, Kout), Ko8
-                    ).reshape(C, R, S, Ko8)
-                    packs = []
-                    for qh in range(stride):
-                        for qw in range(stride):
-                            prh = (qh + pad) % stride
-                            prw = (qw + pad) % stride
-                            sub = wc[:, prh::stride, prw::stride, :]
-                            packs.append(_pad_k(
-                                sub.reshape(C, -1).contiguous()))
-                    return packs
-
-                wd_cls = _packed(w, "dgrad_wcls", build_wd_cls)
-                dpre_img = dpre8.view(N, Ho, Wo, Ko8)
-                dx2d = ext.conv_parity_implicit(
-                    dpre_img, wd_cls, None, _zp(dpre.device), N, Ho, Wo,
-                    Ko8, H, W, C, R, S, stride, pad, 0, 0.0)
-                dx = _as_nchw_view(dx2d.view(N, H, W, C)).to(ctx.dtypes[0])
+                dx = _conv_dgrad_parity(ctx, dpre8)
             else:
-                # strided default: dcol GEMM + col2im gather; when the
-                # geometry qualifies, the fused direct kernel
-                # (conv_dgrad_direct.hip) replaces BOTH in one pass
-                rsc8 = R * S * C8
-                wt = _packed(wp, "wt", lambda: _pad_k(
-                    wp[:, :rsc8].t().contiguous()))   # [rsc8, kout_pad]
-                pact = ctx.prev_act
-                if pact is not None and (
-                        C8 != C
-                        or os.environ.get("GDLJ_NO_ACT_FUSE") == "1"):
-                    pact = None
-                res = None
-                if not _fp8_bwd_on() and _dgrad_direct_on():
-                    p_code, p_slope, p_bias = (
-                        pact if pact is not None else (0, 0.0, None))
-                    res = ext.conv_dgrad_direct(
-                        dpre8, wt, xh if pact is not None else None,
-                        _zp(dpre.device), N, H, W, C8, Ho, Wo, R, S,
-                        stride, pad, p_code, p_slope,
-                        pact is not None and p_bias is not False
-                        and p_bias is not None)
-                if res:
-                    dxh = res[0]
-                    if pact is not None:
-                        dx = _as_nchw_view(dxh).to(ctx.dtypes[0])
-                        deposit_act_fused(
-                            dx, (pact[0], C,
-                                 res[1] if len(res) > 1 else None))
-                    elif C8 != C and dxh.dtype == ctx.dtypes[0]:
-                        trimmed = dxh[..., :C]
-                        dx = _as_nchw_view(trimmed)
-                        deposit_chan_pad(trimmed, dxh)
-                    else:
-                        if C8 != C:
-                            dxh = dxh[..., :C].contiguous()
-                        dx = _as_nchw_view(dxh).to(ctx.dtypes[0])
-                    if (ctx.has_bias and ctx.needs_input_grad[2]
-                            and db is None):
-                        db = ext.col_sum(dpre).to(ctx.dtypes[2])
-                    return (dx, dw, db, None, None, None, None, None,
-                            None)
-                if _fp8_bwd_on():
-                    wtq, _, iwt = _packed(wp, "wt_fp8", lambda: tuple(
-                        ext.fp8_quantize(_pad_k128(wt))))
-                    dq, idy = _quant_delayed(_pad_k128(_pad_k(dpre)), w,
-                                             "dy")
-                    dcol = ext.gemm_tn_fp8(dq, wtq, idy, iwt, None, 0, 0.0)
-                else:
-                    dprep = _pad_k(dpre)
-                    dcol = ext.gemm_tn(dprep, wt, None, 0, 0.0, False)
-                pact = ctx.prev_act
-                if pact is not None and (
-                        C8 != C
-                        or os.environ.get("GDLJ_NO_ACT_FUSE") == "1"):
-                    pact = None
-                if pact is not None:
-                    # the producer's act backward folds into the col2im
-                    # (xh IS the producer's activation output) along with
-                    # its bias-grad column sums; hand both over via the
-                    # side channel so the producer skips its own pass
-                    p_code, p_slope, p_bias = pact
-                    dxh, pdb = ext.col2im_dact(
-                        dcol, N, H, W, C8, Ho, Wo, R, S, stride, pad,
-                        rsc8, xh, p_code, p_slope, p_bias)
-                    dx = _as_nchw_view(dxh).to(ctx.dtypes[0])
-                    deposit_act_fused(
-                        dx, (p_code, C, pdb if p_bias else None))
-                else:
-                    dxh = ext.col2im(dcol, N, H, W, C8, Ho, Wo, R, S,
-                                     stride, pad, rsc8, None, 0, 0.0)
-                    if C8 != C and dxh.dtype == ctx.dtypes[0]:
-                        trimmed = dxh[..., :C]
-                        dx = _as_nchw_view(trimmed)
-                        deposit_chan_pad(trimmed, dxh)
-                    else:
-                        if C8 != C:
-                            dxh = dxh[..., :C].contiguous()
-                        dx = _as_nchw_view(dxh).to(ctx.dtypes[0])
-        if ctx.has_bias and ctx.needs_input_grad[2] and db is None:
-            db = ext.col_sum(dpre).to(ctx.dtypes[2])
+                dx = _conv_dgrad_strided(ctx, dpre, dpre8, xh, wp)
+        if want_bias and db is None:
+            db = hip_ext().col_sum(dpre).to(ctx.dtypes[2])
         return dx, dw, db, None, None, None, None, None, None
 
 
@@ -609,136 +628,118 @@ def conv2d(x, w, b=None, stride=1, padding=0, act="identity", slope=0.2,
 
 
 # ============================================================ conv transpose
+# The three forward routes of _ConvTranspose2d; each returns (yh, stats):
+# the NHWC output (trimmed to Cout) and the fused BN (sum, sumsq) or None.
+def _convt_fwd_s1(geom, xh, w, bias, act, slope, emit_stats):
+    """Stride 1: ONE transposed-gather GEMM with fused bias+activation:
+    y[ho,wo,cout] = act( sum_{r,s,cin}[valid hi=ho+pad-r]
+                         x[hi,wi,cin] * W[cin][cout][r][s] + b )"""
+    ext = hip_ext()
+    N, Cin, Hi, Wi, Cout, R, S, Ho, Wo, stride, pad = geom
+    wt = _packed(w, "convt_fwd_w", lambda: _pad_k(
+        _bf(w.detach().permute(1, 2, 3, 0))      # [Cout,R,S,Cin]
+        .reshape(Cout, R * S * Cin)))
+    stats = None
+    if _fp8_convt_s1_on() and Cin % 16 == 0 and not emit_stats:
+        wtq, _, iw = _fp8_pack(w, "convt_fwd_w_fp8", wt)
+        xq, ix = _quant_delayed(xh, w, "x")
+        y2d = ext.conv_fwd_implicit_fp8(
+            xq, wtq, bias, ix, iw, _zero_page(xh.device, torch.uint8), N,
+            Hi, Wi, Cin, Ho, Wo, R, S, stride, pad, act, slope, 1)
+    else:
+        res = ext.conv_fwd_implicit(
+            xh, wt, bias, _zero_page(xh.device), N, Hi, Wi, Cin, Ho, Wo, R,
+            S, stride, pad, act, slope, 1, 1 if emit_stats else 0)  # mode 1
+        y2d = res[0]
+        if len(res) == 3:
+            stats = (res[1], res[2])
+    return y2d.view(N, Ho, Wo, Cout), stats
+
+
+def _convt_fwd_parity(geom, xh, w, bias, act, slope):
+    """Strided, GDLJ_PARITY: parity-decomposed gathered GEMMs with fused
+    bias+activation (each output parity class reads only its valid taps;
+    no col buffer / col2im pass)."""
+    N, Cin, Hi, Wi, Cout, R, S, Ho, Wo, stride, pad = geom
+    wcls = _packed(w, "convt_fwd_wcls", lambda: _parity_class_packs(
+        _bf(w.detach().permute(1, 2, 3, 0)), stride, pad))  # [Cout,R,S,Cin]
+    y2d = hip_ext().conv_parity_implicit(
+        xh, wcls, bias, _zero_page(xh.device), N, Hi, Wi, Cin, Ho, Wo, Cout,
+        R, S, stride, pad, act, slope)
+    return y2d.view(N, Ho, Wo, Cout), None
+
+
+def _convt_fwd_strided(geom, xh, w, b, bias, act, slope, emit_stats):
+    """Strided default: the parity-direct kernel (conv_dgrad_direct.hip,
+    the strided dgrad's kernel with a bias+act-fwd epilogue and fused BN
+    stats) when the geometry qualifies, else GEMM over Cin + col2im with
+    the same epilogue. Cout is padded to 8 so col2im stays on the
+    vectorized path (scalar col2im for the Cout=3 generator head measured
+    745us vs ~100us vectorized; the wider col write is ~170us)."""
+    ext = hip_ext()
+    N, Cin, Hi, Wi, Cout, R, S, Ho, Wo, stride, pad = geom
+    x2d = _pad_k(xh.reshape(-1, Cin))
+    Co8 = _rup(Cout, 8)
+    def build_w2a():
+        wr = _bf(w.detach().permute(2, 3, 1, 0))        # [R,S,Cout,Cin]
+        if Co8 != Cout:
+            wr = torch.nn.functional.pad(wr, (0, 0, 0, Co8 - Cout))
+        return _pad_k(wr.reshape(R * S * Co8, Cin))
+
+    w2a = _packed(w, "w2a8" if Co8 != Cout else "w2a", build_w2a)
+    if Co8 != Cout and bias is not None:
+        bias = _packed(b, "f32p8", lambda: torch.nn.functional.pad(
+            b.detach().float(), (0, Co8 - Cout)).contiguous())
+    want_stats = bool(emit_stats and Cout % 8 == 0)
+    fp8 = _fp8_convt_strided_on()
+    res = None
+    if _dgrad_direct_on() and not fp8:
+        res = ext.conv_transpose_fwd_direct(
+            x2d, w2a, bias, _zero_page(xh.device), N, Hi, Wi, Ho, Wo, Co8, R,
+            S, stride, pad, act, slope, want_stats)
+    if res:
+        yh, stats = res[0], (res[1], res[2]) if len(res) > 1 else None
+    else:
+        if fp8:
+            w2aq, _, iw2 = _fp8_pack(w, "w2a_fp8", w2a)
+            xq2, ix2 = _quant_delayed(_pad_last(x2d, 128), w, "xT")
+            col = ext.gemm_tn_fp8(xq2, w2aq, ix2, iw2, None, 0, 0.0)
+        else:
+            col = ext.gemm_tn(x2d, w2a, None, 0, 0.0,
+                              False)  # [NPin, RSCo8]
+        if want_stats:
+            yh, ssum, ssq = ext.col2im_stats(
+                col, N, Ho, Wo, Cout, Hi, Wi, R, S, stride, pad,
+                R * S * Cout, bias, act, slope)
+            stats = (ssum, ssq)
+        else:
+            yh, stats = ext.col2im(col, N, Ho, Wo, Co8, Hi, Wi, R, S, stride,
+                                   pad, R * S * Co8, bias, act, slope), None
+    # identity/tanh keep the pad channels zero: act(0 + 0-bias) == 0
+    return _trim_channels(yh, Cout, act in (0, 1)), stats
+
+
 class _ConvTranspose2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, stride: int, pad: int, act: int, slope: float,
                 emit_stats: bool):
-        ext = hip_ext()
         N, Cin, Hi, Wi = x.shape
         _, Cout, R, S = w.shape
         Ho = (Hi - 1) * stride - 2 * pad + R
         Wo = (Wi - 1) * stride - 2 * pad + S
+        geom = (N, Cin, Hi, Wi, Cout, R, S, Ho, Wo, stride, pad)
         xh = _nhwc(x)                       # [N,Hi,Wi,Cin]; Cin % 8 == 0
-        bias = (_packed(b, "f32", lambda: b.detach().float().contiguous())
-                if b is not None else None)
-        stats = None
+        bias = _bias_f32(b)
         if stride == 1:
-            # ONE transposed-gather GEMM with fused bias+activation:
-            # y[ho,wo,cout] = act( sum_{r,s,cin}[valid hi=ho+pad-r]
-            #                      x[hi,wi,cin] * W[cin][cout][r][s] + b )
-            wt = _packed(w, "convt_fwd_w", lambda: _pad_k(
-                _bf(w.detach().permute(1, 2, 3, 0))      # [Cout,R,S,Cin]
-                .reshape(Cout, R * S * Cin)))
-            # stride-1 convT fwd: K = rsc (deep) — fp8 pays; opt-out gate
-            if (FP8_CONV and Cin % 16 == 0 and not emit_stats
-                    and os.environ.get("GDLJ_FP8_CONVT") != "0"):
-                wtq, _, iw = _packed(w, "convt_fwd_w_fp8", lambda: tuple(
-                    ext.fp8_quantize(_pad_k128(wt))))
-                xq, ix = _quant_delayed(xh, w, "x")
-                y2d = ext.conv_fwd_implicit_fp8(
-                    xq, wtq, bias, ix, iw, _zp8(x.device), N, Hi, Wi, Cin,
-                    Ho, Wo, R, S, stride, pad, act, slope, 1)
-            else:
-                res = ext.conv_fwd_implicit(xh, wt, bias, _zp(x.device), N,
-                                            Hi, Wi, Cin, Ho, Wo, R, S,
-                                            stride, pad, act, slope, 1,
-                                            1 if emit_stats else 0)  # mode 1
-                y2d = res[0]
-                if len(res) == 3:
-                    stats = (res[1], res[2])
-            yh = y2d.view(N, Ho, Wo, Cout)
+            yh, stats = _convt_fwd_s1(geom, xh, w, bias, act, slope,
+                                      emit_stats)
         elif PARITY_STRIDED:
-            # strided: parity-decomposed gathered GEMMs with fused
-            # bias+activation (each output parity class reads only its
-            # valid taps; no col buffer / col2im pass)
-            def build_wcls():
-                wc = _bf(w.detach().permute(1, 2, 3, 0))  # [Cout,R,S,Cin]
-                packs = []
-                for qh in range(stride):
-                    for qw in range(stride):
-                        prh = (qh + pad) % stride
-                        prw = (qw + pad) % stride
-                        sub = wc[:, prh::stride, prw::stride, :]
-                        packs.append(_pad_k(sub.reshape(Cout, -1)
-                                            .contiguous()))
-                return packs
-
-            wcls = _packed(w, "convt_fwd_wcls", build_wcls)
-            y2d = ext.conv_parity_implicit(
-                xh, wcls, bias, _zp(x.device), N, Hi, Wi, Cin, Ho, Wo,
-                Cout, R, S, stride, pad, act, slope)
-            yh = y2d.view(N, Ho, Wo, Cout)
+            yh, stats = _convt_fwd_parity(geom, xh, w, bias, act, slope)
         else:
-            # strided default: GEMM over Cin + col2im with fused bias+act
-            # (and optionally the consumer BN's batch statistics).
-            # Cout is padded to 8 so col2im stays on the vectorized path
-            # (scalar col2im for the Cout=3 generator head measured 745us
-            # vs ~100us vectorized; the wider col write is ~170us).
-            x2d = _pad_k(xh.reshape(-1, Cin))
-            Co8 = (Cout + 7) // 8 * 8
-            if Co8 != Cout:
-                def build_w2a8():
-                    wp = _bf(w.detach().permute(2, 3, 1, 0))  # [R,S,Cout,Cin]
-                    wp = torch.nn.functional.pad(wp, (0, 0, 0, Co8 - Cout))
-                    return _pad_k(wp.reshape(R * S * Co8, Cin))
-
-                w2a = _packed(w, "w2a8", build_w2a8)
-                if bias is not None:
-                    bias = _packed(b, "f32p8", lambda: torch.nn.functional.pad(
-                        b.detach().float(), (0, Co8 - Cout)).contiguous())
-            else:
-                w2a = _packed(w, "w2a", lambda: _pad_k(
-                    _bf(w.detach().permute(2, 3, 1, 0))
-                    .reshape(R * S * Cout, Cin)))
-            # parity-direct convT forward (conv_dgrad_direct.hip, same
-            # kernel as the strided dgrad with a bias+act-fwd epilogue
-            # and fused BN stats) — no col buffer / col2im pass
-            res = None
-            if _dgrad_direct_on() and not (
-                    FP8_CONV
-                    and os.environ.get("GDLJ_FP8_CONVT") == "1"):
-                res = ext.conv_transpose_fwd_direct(
-                    x2d, w2a, bias, _zp(x.device), N, Hi, Wi, Ho, Wo,
-                    Co8, R, S, stride, pad, act, slope,
-                    bool(emit_stats and Cout % 8 == 0))
-            if res:
-                yh = res[0]
-                if len(res) > 1:
-                    stats = (res[1], res[2])
-            else:
-                # strided convT dcol: K = Cin <= 1024 (thin,
-                # memory-bound): fp8 measured -2% end-to-end at
-                # dcgan128 b2048 (profiles/fp8_bwd_ab.md) — opt-in only
-                if FP8_CONV and os.environ.get("GDLJ_FP8_CONVT") == "1":
-                    w2aq, _, iw2 = _packed(w, "w2a_fp8", lambda: tuple(
-                        ext.fp8_quantize(_pad_k128(w2a))))
-                    xq2, ix2 = _quant_delayed(_pad_k128(x2d), w, "xT")
-                    col = ext.gemm_tn_fp8(xq2, w2aq, ix2, iw2, None, 0,
-                                          0.0)
-                else:
-                    col = ext.gemm_tn(x2d, w2a, None, 0, 0.0,
-                                      False)  # [NPin, RSCo8]
-            if res and len(res) > 1:
-                pass                           # fused stats already set
-            elif not res and emit_stats and Cout % 8 == 0:
-                yh, ssum, ssq = ext.col2im_stats(
-                    col, N, Ho, Wo, Cout, Hi, Wi, R, S, stride, pad,
-                    R * S * Cout, bias, act, slope)
-                stats = (ssum, ssq)
-            else:
-                if not res:
-                    yh = ext.col2im(col, N, Ho, Wo, Co8, Hi, Wi, R, S,
-                                    stride, pad, R * S * Co8, bias, act,
-                                    slope)
-                if Co8 != Cout:
-                    if act in (0, 1):  # identity/tanh: act(0 + 0-bias) == 0
-                        yh_pad = yh
-                        yh = yh_pad[..., :Cout]
-                        deposit_chan_pad(yh, yh_pad)
-                    else:
-                        yh = yh[..., :Cout].contiguous()
+            yh, stats = _convt_fwd_strided(geom, xh, w, b, bias, act, slope,
+                                           emit_stats)
         ctx.save_for_backward(xh, yh)
-        ctx.geom = (N, Cin, Hi, Wi, Cout, R, S, Ho, Wo, stride, pad)
+        ctx.geom = geom
         ctx.act, ctx.slope = act, slope
         ctx.has_bias = b is not None
         ctx.dtypes = (x.dtype, w.dtype, b.dtype if b is not None else None)
@@ -754,100 +755,61 @@ class _ConvTranspose2d(torch.autograd.Function):
         xh, yh = ctx.saved_tensors
         w = ctx.wref
         N, Cin, Hi, Wi, Cout, R, S, Ho, Wo, stride, pad = ctx.geom
-        rsco = R * S * Cout
-        rscop = _rup64(rsco)
         fused = take_act_fused(dy)
-        db = None
         want_bias = ctx.has_bias and ctx.needs_input_grad[2]
-        Co8 = (Cout + 7) // 8 * 8
-        dpre8 = None
+        Co8 = _rup(Cout, 8)
         # 3-channel image boundary pass-through: when the downstream
         # conv's dgrad deposited the PADDED dy and the forward deposited
         # the padded y, act backward runs at Co8 width (the pad lanes are
         # exact zeros through tanh/identity) and no trim/re-pad copies
         # are paid on either side of the boundary.
+        dy_pad = y_pad = None
         if fused is None and Co8 != Cout:
             dy_pad = take_chan_pad(dy, Co8)
             y_pad = take_chan_pad(yh, Co8) if dy_pad is not None else None
-            if dy_pad is not None and (y_pad is not None or ctx.act == 0):
-                if ctx.act:
-                    if want_bias:
-                        dp, db_f = ext.act_bwd_bias(
-                            dy_pad.reshape(-1, Co8),
-                            y_pad.reshape(-1, Co8), ctx.act, ctx.slope)
-                        db = db_f[:Cout].to(ctx.dtypes[2])
-                    else:
-                        dp = ext.act_bwd(dy_pad.reshape(-1, Co8),
-                                         y_pad.reshape(-1, Co8), ctx.act,
-                                         ctx.slope)
-                    dpre8 = dp.view(N, Ho, Wo, Co8)
-                else:
-                    dpre8 = dy_pad
-        if dpre8 is None:
-            dyh = _nhwc(dy)                   # [N,Ho,Wo,Cout]
-            if fused is not None and fused[0] == ctx.act and \
-                    fused[1] == Cout:
-                # consumer BN already applied act backward + bias grad
-                dpre_img = dyh
-                if want_bias and fused[2] is not None:
-                    db = fused[2].to(ctx.dtypes[2])
-            elif ctx.act and want_bias and Cout % 8 == 0:
-                dpre, db_f = ext.act_bwd_bias(
-                    dyh.reshape(-1, Cout),
-                    yh.reshape(-1, Cout).contiguous(), ctx.act, ctx.slope)
-                db = db_f.to(ctx.dtypes[2])
-                dpre_img = dpre.view(N, Ho, Wo, Cout)
-            elif ctx.act:
-                dpre = ext.act_bwd(dyh.reshape(-1, Cout),
-                                   yh.reshape(-1, Cout).contiguous(),
-                                   ctx.act, ctx.slope)
-                dpre_img = dpre.view(N, Ho, Wo, Cout)
-            else:
-                dpre_img = dyh
-            dpre_img = dpre_img.contiguous()
-            dpre8 = _pad_channels(dpre_img, Co8)
+        if dy_pad is not None and (y_pad is not None or ctx.act == 0):
+            dpre, db = _act_bwd(ctx, dy_pad, y_pad, Co8, Cout, None,
+                                want_bias)
+            dpre8 = dpre.view(N, Ho, Wo, Co8)
+        else:
+            dpre, db = _act_bwd(ctx, _nhwc(dy), yh, Cout, Cout, fused,
+                                want_bias)
+            dpre8 = _pad_channels(dpre.view(N, Ho, Wo, Cout), Co8)
         npq = N * Hi * Wi
         dx = dw = None
         if ctx.needs_input_grad[0]:
             # dx[np_in][cin] = sum_{r,s,cout} dpre[ho=hi*s-p+r..][cout]
             #                  * W[cin][cout][r][s]  (forward-gather, mode 0)
-            def build_w2b():
-                wc = _bf(w.detach().permute(0, 2, 3, 1))   # [Cin,R,S,Cout]
-                wc = _pad_channels(wc.reshape(Cin * R * S, 1, 1, Cout),
-                                   Co8).reshape(Cin, R * S * Co8)
-                return _pad_k(wc)
-
-            w2b = _packed(w, "convt_dgrad_w", build_w2b)
+            w2b = _packed(w, "convt_dgrad_w", lambda: _pad_k(
+                _weight_taps(w, (0, 2, 3, 1), Co8)     # [Cin,R,S,Co8]
+                .reshape(Cin, R * S * Co8)))
             if _fp8_bwd_on() and Co8 % 16 == 0:
-                w2bq, _, iw2b = _packed(w, "convt_dgrad_w_fp8",
-                                        lambda: tuple(
-                                            ext.fp8_quantize(
-                                                _pad_k128(w2b))))
+                w2bq, _, iw2b = _fp8_pack(w, "convt_dgrad_w_fp8", w2b)
                 dq, idy = _quant_delayed(dpre8, w, "dy")
                 dx2d = ext.conv_fwd_implicit_fp8(
-                    dq, w2bq, None, idy, iw2b, _zp8(dpre8.device), N, Ho,
-                    Wo, Co8, Hi, Wi, R, S, stride, pad, 0, 0.0, 0)
+                    dq, w2bq, None, idy, iw2b,
+                    _zero_page(dpre8.device, torch.uint8), N, Ho, Wo, Co8,
+                    Hi, Wi, R, S, stride, pad, 0, 0.0, 0)
             else:
-                dx2d = ext.conv_fwd_implicit(dpre8, w2b, None,
-                                             _zp(dpre8.device), N, Ho, Wo,
-                                             Co8, Hi, Wi, R, S, stride,
-                                             pad, 0, 0.0, 0, 0)[0]
+                dx2d = ext.conv_fwd_implicit(
+                    dpre8, w2b, None, _zero_page(dpre8.device), N, Ho, Wo,
+                    Co8, Hi, Wi, R, S, stride, pad, 0, 0.0, 0, 0)[0]
             dx = _as_nchw_view(dx2d.view(N, Hi, Wi, Cin)).to(ctx.dtypes[0])
         if ctx.needs_input_grad[1]:
             # wgrad: dW[(r,s,cout)][cin] = sum_np im2col(dpre)[np][rs*cout]
             #        * x[np][cin]  (gathered-A NT over dOut)
             rsco8 = R * S * Co8
-            rscop8 = _rup64(rsco8)
+            rscop8 = _rup(rsco8, 64)
             x2d = _pad_k(xh.reshape(-1, Cin))
             sk = _splitk_for((rscop8 + 127) // 128,
                              (x2d.shape[1] + 127) // 128, (npq + 63) // 64)
             dw2a = ext.gemm_nt_implicit(
                 dpre8, x2d, 1, rscop8, x2d.shape[1], npq,
                 _dims(N, Ho, Wo, Co8, Hi, Wi, R, S, stride, pad),
-                sk, _zp(x2d.device))
+                sk, _zero_page(x2d.device))
             dw = (dw2a[:rsco8, :Cin].reshape(R, S, Co8, Cin)[:, :, :Cout]
                   .permute(3, 2, 0, 1).contiguous().to(ctx.dtypes[1]))
-        if ctx.has_bias and ctx.needs_input_grad[2] and db is None:
+        if want_bias and db is None:
             db = ext.col_sum(dpre8.reshape(-1, Co8))[:Cout].to(
                 ctx.dtypes[2])
         return dx, dw, db, None, None, None, None, None
@@ -910,7 +872,7 @@ def batch_norm(x, weight, bias, running_mean, running_var, training,
     else:
         x2 = _bf(x)
     if bwd_act is not None and (x2.shape[-1] % 8 != 0
-                                or os.environ.get("GDLJ_NO_ACT_FUSE") == "1"):
+                                or not _act_fuse_on()):
         bwd_act = None
     if training:
         y2 = _BatchNorm.apply(x2, weight, bias, running_mean, running_var,
