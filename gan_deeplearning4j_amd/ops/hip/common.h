@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
+#include <stdlib.h>
 
 #include "launch_abi.h"
 
@@ -16,6 +17,7 @@ typedef __attribute__((ext_vector_type(16))) float   f32x16;
 typedef __attribute__((ext_vector_type(4))) short    s16x4;
 typedef __attribute__((ext_vector_type(8))) short    s16x8;
 typedef __attribute__((ext_vector_type(4))) int      i32x4;
+typedef __attribute__((ext_vector_type(8))) __bf16   bf16x8;
 
 using bf16 = __hip_bfloat16;
 
@@ -82,6 +84,45 @@ DEV_INLINE unsigned fdiv(unsigned n, FastDiv f) {
 
 DEV_INLINE unsigned fmod_(unsigned n, FastDiv f, unsigned q) {
   return n - q * (unsigned)f.d;
+}
+
+// ------------------------------------------------------- LDS-DMA staging
+// one 16B global -> LDS copy per lane; the LDS destination is wave-uniform
+// (lane-linear behind it), so swizzles go through the SOURCE address
+#define GLDS16(gsrc, ldst)                                                    \
+  __builtin_amdgcn_global_load_lds(                                          \
+      (const __attribute__((address_space(1))) unsigned int*)(gsrc),          \
+      (__attribute__((address_space(3))) unsigned int*)(ldst), 16, 0, 0)
+
+// --------------------------------------------------------- XCD block remap
+// Bijective XCD-aware remap of a linear block id over nwg blocks: hardware
+// deals consecutive ids round-robin to the 8 XCDs; this hands each XCD a
+// contiguous run of tiles instead (L2 locality), exact for any nwg.
+// Callers read gridDim into a local before the call: evaluating it as an
+// argument changes register allocation in gemm_tn_kshort<128, true>.
+DEV_INLINE int xcd_remap(int bid, int nwg) {
+  if (nwg >= 8) {
+    int q = nwg / 8, r = nwg % 8;
+    int xcd = bid % 8, idx = bid / 8;
+    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  }
+  return bid;
+}
+
+// ------------------------------------------------- launcher env gates (host)
+// Use as a function-local `static const int v = env_flag(...)`: the gate is
+// read once, at the first launch that consults it.
+// on/off gate: only a leading '0' turns a default-on gate off, only a
+// leading '1' turns a default-off gate on
+static inline int env_flag(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return (e != nullptr && e[0] == (dflt ? '0' : '1')) ? !dflt : dflt;
+}
+
+// integer gate (atoi parse)
+static inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e != nullptr ? atoi(e) : dflt;
 }
 
 #define HIP_CHECK_LAST()                                                     \

@@ -37,13 +37,6 @@
 
 #include "common.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-
-#define GLDS16(gsrc, ldst)                                                    \
-  __builtin_amdgcn_global_load_lds(                                          \
-      (const __attribute__((address_space(1))) unsigned int*)(gsrc),          \
-      (__attribute__((address_space(3))) unsigned int*)(ldst), 16, 0, 0)
-
 namespace cdd {
 constexpr int BN = 64;
 constexpr int WSLICE_B = 16 * 1024;      // one [64c][128co] slice (2 subs)
@@ -51,7 +44,7 @@ constexpr int WBUF_B = 2 * WSLICE_B;     // double buffer; >= ctile bytes
 }  // namespace cdd
 
 // 64-row x 64-k staged sub-tile, same swizzled layout/frag read as the
-// proven tn layout (gemm.hip tn_stage / tn_frag geometry).
+// proven tn layout (conv_gather.h tn_stage_rows / gemm.hip tn_frag geometry).
 DEV_INLINE void cdd_stage_w64(const unsigned short* __restrict__ g,
                               long ldk, int k0, char* lds) {
   const int t = threadIdx.x;
@@ -107,13 +100,8 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct(
   auto wbuf = [&](int i) -> char* { return lds + rgn_b + i * WSLICE_B; };
 
   // XCD-aware swizzle over class-pixel tiles
-  int nwgx = gridDim.x;
-  int bidx = blockIdx.x;
-  if (nwgx >= 8) {
-    int q = nwgx / 8, r = nwgx % 8;
-    int xcd = bidx % 8, idx = bidx / 8;
-    bidx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int nwgx = gridDim.x;
+  const int bidx = xcd_remap(blockIdx.x, nwgx);
   const int np0 = bidx * BM;
   const int hwc = Hc * Wc;
   const int n = np0 / hwc;         // once per block: plain div is fine

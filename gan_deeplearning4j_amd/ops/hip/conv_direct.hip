@@ -19,13 +19,6 @@
 
 #include "common.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-
-#define GLDS16(gsrc, ldst)                                                    \
-  __builtin_amdgcn_global_load_lds(                                          \
-      (const __attribute__((address_space(1))) unsigned int*)(gsrc),          \
-      (__attribute__((address_space(3))) unsigned int*)(ldst), 16, 0, 0)
-
 namespace cdir {
 constexpr int BM = 128, BN = 64, BK = 64;
 constexpr int IMG_B = 24 * 1024;   // padded image region budget
@@ -76,13 +69,8 @@ __global__ __launch_bounds__(256, 2) void conv_direct_smallc(
   const int Wp_ = W + 2 * pad;
   // np tile -> (n, ho0): blocks walk np linearly; (Ho*Wo)%128==0 keeps a
   // block inside one sample
-  int nwgx = gridDim.x;
-  int bidx = blockIdx.x;
-  if (nwgx >= 8) {
-    int q = nwgx / 8, r = nwgx % 8;
-    int xcd = bidx % 8, idx = bidx / 8;
-    bidx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int nwgx = gridDim.x;
+  const int bidx = xcd_remap(blockIdx.x, nwgx);
   const int np0 = bidx * BM;
   // (Ho*Wo) % 128 == 0 and Wo | 128 => np0 is a whole-output-row boundary
   // within one sample; once per block, plain integer div is fine.

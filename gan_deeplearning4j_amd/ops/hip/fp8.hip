@@ -9,14 +9,9 @@
 // double-buffered LDS staged by 16B global_load_lds with the im2col gather
 // fused into the source address (zero-page redirect for OOB/pad).
 
-#include "common.h"
+#include "conv_gather.h"
 
 typedef __attribute__((ext_vector_type(8))) float f32x8;
-
-#define GLDS16(gsrc, ldst)                                                    \
-  __builtin_amdgcn_global_load_lds(                                          \
-      (const __attribute__((address_space(1))) unsigned int*)(gsrc),          \
-      (__attribute__((address_space(3))) unsigned int*)(ldst), 16, 0, 0)
 
 // ----------------------------------------------------------- quantization
 // amax via atomicMax on the positive-float bit pattern
@@ -134,118 +129,10 @@ __global__ void fp8_roll_scale(unsigned* __restrict__ amax_bits,
 // bf16 FLOP rate, i.e. half the 5 PF fp8 peak).
 constexpr int F8_BM = 128, F8_BN = 128, F8_BK = 128;
 constexpr int F8_TILE_B = F8_BM * F8_BK;  // bytes (1B/elem)
-
-DEV_INLINE void f8_stage(const unsigned char* __restrict__ g, int row0,
-                         int nrows, long ldk, int k0, char* lds) {
-  const int t = threadIdx.x;
-  const int wid = t >> 6;
-  #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int chunk = i * 256 + t;       // 1024 chunks = row*8 + slot16
-    int row = chunk >> 3;
-    int slot = chunk & 7;
-    int gslot = slot ^ (row & 7);
-    int grow = min(row0 + row, nrows - 1);
-    const unsigned char* src = g + (long)grow * ldk + k0 + gslot * 16;
-    char* dst = lds + (i * 256 + wid * 64) * 16;
-    GLDS16(src, dst);
-  }
-}
-
-DEV_INLINE void k_decode_f8(const ConvGather& g, unsigned k, int& r, int& s,
-                            int& c) {
-  unsigned rs = fdiv(k, g.fC);
-  c = (int)(k - rs * g.C);
-  unsigned rr = fdiv(rs, g.fS);
-  s = (int)(rs - rr * g.S);
-  r = (int)rr;
-}
-
-// NOTE: 16-fp8 chunks must not straddle (r,s) boundaries -> requires
-// C % 16 == 0 (enforced by the binding).
-// Row decode hoisted out of the K-loop (same scheme as TnGatherStager in
-// gemm.hip): each thread stages the same 4 rows every K-step.
-struct F8GatherStager {
-  long base[4];      // (long)n * H*W*C element offset per chunk
-  int h0[4], w0[4];  // mode-adjusted spatial bases per chunk
-
-  DEV_INLINE void init(const ConvGather& g, int row0, int nrows) {
-    const int t = threadIdx.x;
-    #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int row = (i * 256 + t) >> 3;
-      int np = min(row0 + row, nrows - 1);
-      unsigned q1 = fdiv((unsigned)np, g.fWo);
-      int wo = (int)((unsigned)np - q1 * g.Wo);
-      unsigned q2 = fdiv(q1, g.fHo);
-      int ho = (int)(q1 - q2 * g.Ho);
-      base[i] = (long)(int)q2 * g.H * g.W * g.C;
-      if (g.mode == 0) {
-        h0[i] = ho * g.stride - g.pad;
-        w0[i] = wo * g.stride - g.pad;
-      } else if (g.mode == 2) {
-        h0[i] = ho + g.off_h;
-        w0[i] = wo + g.off_w;
-      } else {
-        h0[i] = ho + g.pad;
-        w0[i] = wo + g.pad;
-      }
-    }
-  }
-
-  DEV_INLINE void stage(const unsigned char* __restrict__ img,
-                        const ConvGather& g,
-                        const unsigned char* __restrict__ zp, int k0,
-                        char* lds) const {
-    const int t = threadIdx.x;
-    const int wid = t >> 6;
-    #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int chunk = i * 256 + t;
-      int row = chunk >> 3;
-      int slot = chunk & 7;
-      int gslot = slot ^ (row & 7);
-      int k = k0 + gslot * 16;  // 16 fp8 channels per chunk
-      const unsigned char* src = zp;
-      if (k < g.rsc) {
-        int r, s, c;
-        k_decode_f8(g, (unsigned)k, r, s, c);
-        int hi, wi;
-        bool valid;
-        if (g.mode == 0) {
-          hi = h0[i] + r;
-          wi = w0[i] + s;
-          valid = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
-        } else if (g.mode == 2) {
-          hi = h0[i] - r;
-          wi = w0[i] - s;
-          valid = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
-        } else {
-          int hop = h0[i] - r;
-          int wop = w0[i] - s;
-          if (hop < 0 || wop < 0) {
-            valid = false;
-            hi = wi = 0;
-          } else {
-            unsigned qh = fdiv((unsigned)hop, g.fStride);
-            unsigned qw = fdiv((unsigned)wop, g.fStride);
-            valid = (hop == (int)(qh * g.stride)) &&
-                    (wop == (int)(qw * g.stride)) && (int)qh < g.H &&
-                    (int)qw < g.W;
-            hi = (int)qh;
-            wi = (int)qw;
-          }
-        }
-        if (valid) src = img + base[i] + (long)(hi * g.W + wi) * g.C + c;
-      }
-      char* dst = lds + (i * 256 + wid * 64) * 16;
-      GLDS16(src, dst);
-    }
-  }
-};
+// Staged by conv_gather.h's tn_stage_rows / TnGatherStager at 1-byte
+// elements: a 16B chunk is 16 fp8 channels.
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
 
 // fragment = 32 consecutive fp8 (lane's K window kq*32) as two XOR-swizzled
 // 16B LDS reads; rows are 128B (8 slots of 16B)
@@ -273,13 +160,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_fp8_core(
     return lds + F8_TILE_B + (i ? 2 * F8_TILE_B : 0);
   };
 
-  int nwgx = gridDim.x;
-  int bidx = blockIdx.x;
-  if (nwgx >= 8) {
-    int q = nwgx / 8, r = nwgx % 8;
-    int xcd = bidx % 8, idx = bidx / 8;
-    bidx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int nwgx = gridDim.x;
+  const int bidx = xcd_remap(blockIdx.x, nwgx);
   const int m0 = bidx * F8_BM;
   const int n0 = blockIdx.y * F8_BN;
   const int wid = threadIdx.x >> 6;
@@ -294,14 +176,14 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_fp8_core(
     for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
   const int ntiles = K / F8_BK;
-  F8GatherStager gs;
+  TnGatherStager<256, unsigned char> gs;
   if (GATHER_A) {
     gs.init(ga, m0, M);
     gs.stage(A, ga, zp, 0, abuf(0));
   } else {
-    f8_stage(A, m0, M, lda, 0, abuf(0));
+    tn_stage_rows<256, 4>(A, m0, M, lda, 0, abuf(0));
   }
-  f8_stage(B, n0, N, ldb, 0, bbuf(0));
+  tn_stage_rows<256, 4>(B, n0, N, ldb, 0, bbuf(0));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -311,8 +193,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_fp8_core(
       if (GATHER_A)
         gs.stage(A, ga, zp, (t + 1) * F8_BK, abuf(cur ^ 1));
       else
-        f8_stage(A, m0, M, lda, (t + 1) * F8_BK, abuf(cur ^ 1));
-      f8_stage(B, n0, N, ldb, (t + 1) * F8_BK, bbuf(cur ^ 1));
+        tn_stage_rows<256, 4>(A, m0, M, lda, (t + 1) * F8_BK, abuf(cur ^ 1));
+      tn_stage_rows<256, 4>(B, n0, N, ldb, (t + 1) * F8_BK, bbuf(cur ^ 1));
     }
     const char* Al = abuf(cur);
     const char* Bl = bbuf(cur);
@@ -368,16 +250,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_fp8_core(
       int gcol = n0 + seg * 8;
       if (grow < M && gcol + 8 <= N) {
         long crow = grow;
-        if (GATHER_A && ga.mode == 2) {
-          int n2, h2, w2;
-          unsigned q1 = fdiv((unsigned)grow, ga.fWo);
-          w2 = (int)((unsigned)grow - q1 * ga.Wo);
-          unsigned q2 = fdiv(q1, ga.fHo);
-          h2 = (int)(q1 - q2 * ga.Ho);
-          n2 = (int)q2;
-          crow = ((long)n2 * ga.oH + h2 * ga.stride + ga.oqh) * ga.oW +
-                 w2 * ga.stride + ga.oqw;
-        }
+        if (GATHER_A && ga.mode == 2) crow = scatter_row(ga, grow);
         *(s16x8*)(&C[crow * N + gcol]) =
             *(const s16x8*)(ctile + row * 128 + seg * 8);
       }

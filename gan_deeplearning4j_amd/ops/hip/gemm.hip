@@ -18,182 +18,25 @@
 //  gemm_nt:  C[M][N] (fp32) += sum_k A[k][M] * B[k][N]
 //            contraction over ROWS of both operands: weight-grad
 //            (A=dOut, B=im2col). 128x128x64 tile, 8 waves, double-buffered
-//            register staging (loads for tile t+1 issued before tile t's
-//            MFMAs), split-K over blockIdx.z with fp32 atomics. Either
-//            operand may be gathered from an NHWC image (implicit wgrad).
+//            LDS staged with global_load_lds (operand rows land coalesced;
+//            the stage for tile t+1 is issued before tile t's MFMAs),
+//            fragments read by ds_read_b64_tr_b16 (hardware transpose),
+//            split-K over blockIdx.z with fp32 atomics. Either operand may
+//            be gathered from an NHWC image (implicit wgrad).
 //
 // K must be a multiple of 64 for gemm_tn (callers pad; gathered A pads by
 // zero-page); gemm_nt handles arbitrary K by zero-fill.
+//
+// The gather address rule and the [row][8 slot] tile stagers are shared with
+// fp8.hip and the 8-phase kernels: conv_gather.h.
 
-#include "common.h"
-#include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-
-#define GLDS16(gsrc, ldst)                                                    \
-  __builtin_amdgcn_global_load_lds(                                          \
-      (const __attribute__((address_space(1))) unsigned int*)(gsrc),          \
-      (__attribute__((address_space(3))) unsigned int*)(ldst), 16, 0, 0)
-
-// decode np -> (n, ho, wo)
-DEV_INLINE void np_decode(const ConvGather& g, unsigned np, int& n, int& ho,
-                          int& wo) {
-  unsigned q1 = fdiv(np, g.fWo);
-  wo = (int)(np - q1 * g.Wo);
-  unsigned q2 = fdiv(q1, g.fHo);
-  ho = (int)(q1 - q2 * g.Ho);
-  n = (int)q2;
-}
-
-// decode k -> (r, s, c); caller checks k < rsc
-DEV_INLINE void k_decode(const ConvGather& g, unsigned k, int& r, int& s,
-                         int& c) {
-  unsigned rs = fdiv(k, g.fC);
-  c = (int)(k - rs * g.C);
-  unsigned rr = fdiv(rs, g.fS);
-  s = (int)(rs - rr * g.S);
-  r = (int)rr;
-}
-
-// source address for grid position (ho,wo) + kernel offset (r,s), channel c;
-// returns nullptr-sentinel via 'valid'
-DEV_INLINE const unsigned short* gather_addr(
-    const ConvGather& g, const unsigned short* img, int n, int ho, int wo,
-    int r, int s, int c, bool& valid) {
-  int hi, wi;
-  if (g.mode == 0) {
-    hi = ho * g.stride - g.pad + r;
-    wi = wo * g.stride - g.pad + s;
-    valid = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
-  } else if (g.mode == 2) {
-    hi = ho + g.off_h - r;
-    wi = wo + g.off_w - s;
-    valid = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
-  } else {
-    int hop = ho + g.pad - r;
-    int wop = wo + g.pad - s;
-    if (hop < 0 || wop < 0) {
-      valid = false;
-      hi = wi = 0;
-    } else {
-      unsigned qh = fdiv((unsigned)hop, g.fStride);
-      unsigned qw = fdiv((unsigned)wop, g.fStride);
-      valid = (hop == (int)(qh * g.stride)) &&
-              (wop == (int)(qw * g.stride)) && (int)qh < g.H && (int)qw < g.W;
-      hi = (int)qh;
-      wi = (int)qw;
-    }
-  }
-  return img + (((long)n * g.H + hi) * g.W + wi) * g.C + c;
-}
+#include "conv_gather.h"
 
 // ---------------------------------------------------------------------------
 // TN kernel
 // ---------------------------------------------------------------------------
 constexpr int TN_BM = 128, TN_BN = 128, TN_BK = 64;
 constexpr int TN_TILE_B = TN_BM * TN_BK * 2;  // 16 KiB per operand tile
-
-// stage one plain operand tile: 1024 16B chunks, 4 glds per thread
-DEV_INLINE void tn_stage(const unsigned short* __restrict__ g, int row0,
-                         int nrows, long ldk, int k0, char* lds) {
-  const int t = threadIdx.x;
-  const int wid = t >> 6;
-  #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int chunk = i * 256 + t;         // = row*8 + slot
-    int row = chunk >> 3;
-    int slot = chunk & 7;
-    int gslot = slot ^ (row & 7);    // inverse swizzle on the source
-    int grow = min(row0 + row, nrows - 1);
-    const unsigned short* src = g + (long)grow * ldk + k0 + gslot * 8;
-    char* dst = lds + (i * 256 + wid * 64) * 16;  // wave-uniform, lane-linear
-    GLDS16(src, dst);
-  }
-}
-
-// implicit-GEMM stage: A rows are im2col rows gathered from the NHWC image.
-// The (np -> n,ho,wo) row decode and the n-plane base offset are invariant
-// across the whole K-loop (each thread stages the same 4 rows every step),
-// so they are hoisted into registers once (init) and only the cheap k part
-// (tap + channel) is decoded per chunk per step (stage).
-template <int NTH>  // block thread count: 4 chunks staged per thread
-struct TnGatherStagerT {
-  long base[4];        // (long)n * H*W*C element offset per chunk
-  int h0[4], w0[4];    // mode-adjusted spatial bases per chunk
-
-  DEV_INLINE void init(const ConvGather& g, int row0, int nrows) {
-    const int t = threadIdx.x;
-    #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int row = (i * NTH + t) >> 3;
-      int np = min(row0 + row, nrows - 1);
-      int n, ho, wo;
-      np_decode(g, (unsigned)np, n, ho, wo);
-      base[i] = (long)n * g.H * g.W * g.C;
-      if (g.mode == 0) {
-        h0[i] = ho * g.stride - g.pad;
-        w0[i] = wo * g.stride - g.pad;
-      } else if (g.mode == 2) {
-        h0[i] = ho + g.off_h;
-        w0[i] = wo + g.off_w;
-      } else {
-        h0[i] = ho + g.pad;
-        w0[i] = wo + g.pad;
-      }
-    }
-  }
-
-  DEV_INLINE void stage(const unsigned short* __restrict__ img,
-                        const ConvGather& g,
-                        const unsigned short* __restrict__ zp, int k0,
-                        char* lds) const {
-    const int t = threadIdx.x;
-    const int wid = t >> 6;
-    #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int chunk = i * NTH + t;
-      int row = chunk >> 3;
-      int slot = chunk & 7;
-      int gslot = slot ^ (row & 7);
-      int k = k0 + gslot * 8;
-      const unsigned short* src = zp;
-      if (k < g.rsc) {
-        int r, s, c;
-        k_decode(g, (unsigned)k, r, s, c);
-        int hi, wi;
-        bool valid;
-        if (g.mode == 0) {
-          hi = h0[i] + r;
-          wi = w0[i] + s;
-          valid = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
-        } else if (g.mode == 2) {
-          hi = h0[i] - r;
-          wi = w0[i] - s;
-          valid = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
-        } else {
-          int hop = h0[i] - r;
-          int wop = w0[i] - s;
-          if (hop < 0 || wop < 0) {
-            valid = false;
-            hi = wi = 0;
-          } else {
-            unsigned qh = fdiv((unsigned)hop, g.fStride);
-            unsigned qw = fdiv((unsigned)wop, g.fStride);
-            valid = (hop == (int)(qh * g.stride)) &&
-                    (wop == (int)(qw * g.stride)) && (int)qh < g.H &&
-                    (int)qw < g.W;
-            hi = (int)qh;
-            wi = (int)qw;
-          }
-        }
-        if (valid) src = img + base[i] + (long)(hi * g.W + wi) * g.C + c;
-      }
-      char* dst = lds + (i * NTH + wid * 64) * 16;
-      GLDS16(src, dst);
-    }
-  }
-};
-using TnGatherStager = TnGatherStagerT<256>;
 
 DEV_INLINE bf16x8 tn_frag(const char* lds, int row, int kslot) {
   int byte = row * 128 + ((kslot ^ (row & 7)) * 16);
@@ -215,13 +58,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_core(
   };
 
   // XCD-aware swizzle (T1, bijective variant) over M-tiles
-  int nwgx = gridDim.x;
-  int bidx = blockIdx.x;
-  if (nwgx >= 8) {
-    int q = nwgx / 8, r = nwgx % 8;
-    int xcd = bidx % 8, idx = bidx / 8;
-    bidx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int nwgx = gridDim.x;
+  const int bidx = xcd_remap(blockIdx.x, nwgx);
   const int m0 = bidx * TN_BM;
   const int n0 = blockIdx.y * TN_BN;
 
@@ -237,14 +75,14 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_core(
     for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
   const int ntiles = K / TN_BK;
-  TnGatherStager gs;
+  TnGatherStager<256, unsigned short> gs;
   if (GATHER_A) {
     gs.init(ga, m0, M);
     gs.stage(A, ga, zp, 0, abuf(0));
   } else {
-    tn_stage(A, m0, M, lda, 0, abuf(0));
+    tn_stage_rows<256, 4>(A, m0, M, lda, 0, abuf(0));
   }
-  tn_stage(B, n0, N, ldb, 0, bbuf(0));
+  tn_stage_rows<256, 4>(B, n0, N, ldb, 0, bbuf(0));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -254,8 +92,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_core(
       if (GATHER_A)
         gs.stage(A, ga, zp, (t + 1) * TN_BK, abuf(cur ^ 1));
       else
-        tn_stage(A, m0, M, lda, (t + 1) * TN_BK, abuf(cur ^ 1));
-      tn_stage(B, n0, N, ldb, (t + 1) * TN_BK, bbuf(cur ^ 1));
+        tn_stage_rows<256, 4>(A, m0, M, lda, (t + 1) * TN_BK, abuf(cur ^ 1));
+      tn_stage_rows<256, 4>(B, n0, N, ldb, (t + 1) * TN_BK, bbuf(cur ^ 1));
     }
     const char* Al = abuf(cur);
     const char* Bl = bbuf(cur);
@@ -308,12 +146,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_core(
       int gcol = n0 + seg * 8;
       if (grow < M && gcol < N) {
         long crow = grow;
-        if (GATHER_A && ga.mode == 2) {
-          int n, h2, w2;
-          np_decode(ga, (unsigned)grow, n, h2, w2);
-          crow = ((long)n * ga.oH + h2 * ga.stride + ga.oqh) * ga.oW +
-                 w2 * ga.stride + ga.oqw;
-        }
+        if (GATHER_A && ga.mode == 2) crow = scatter_row(ga, grow);
         s16x8 v = *(const s16x8*)(ctile + row * 128 + seg * 8);
         if (gcol + 8 <= N) {
           *(s16x8*)(&C[crow * N + gcol]) = v;
@@ -363,12 +196,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_core(
         int row = m0 + wr * 64 + mi * 16 + fq * 4 + r;
         if (row >= M) continue;
         long crow = row;
-        if (GATHER_A && ga.mode == 2) {
-          int n, h2, w2;
-          np_decode(ga, (unsigned)row, n, h2, w2);
-          crow = ((long)n * ga.oH + h2 * ga.stride + ga.oqh) * ga.oW +
-                 w2 * ga.stride + ga.oqw;
-        }
+        if (GATHER_A && ga.mode == 2) crow = scatter_row(ga, row);
         float v = act_fwd(acc[mi][ni][r] + bv, act, slope);
         if (C != nullptr)
           C[crow * N + col] = f2bf(v);
@@ -399,13 +227,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kshort(
   auto abuf = [&](int t) -> char* { return lds + t * TN_TILE_B; };
   auto bbuf = [&](int t) -> char* { return lds + (NT + t) * TN_TILE_B; };
 
-  int nwgx = gridDim.x;
-  int bidx = blockIdx.x;
-  if (nwgx >= 8) {
-    int q = nwgx / 8, r = nwgx % 8;
-    int xcd = bidx % 8, idx = bidx / 8;
-    bidx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int nwgx = gridDim.x;
+  const int bidx = xcd_remap(blockIdx.x, nwgx);
   const int m0 = bidx * TN_BM;
   const int n0 = blockIdx.y * TN_BN;
   const int wid = threadIdx.x >> 6;
@@ -419,15 +242,15 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kshort(
     #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
-  TnGatherStager gs;
+  TnGatherStager<256, unsigned short> gs;
   if (GATHER_A) gs.init(ga, m0, M);
   #pragma unroll
   for (int t = 0; t < NT; ++t) {
     if (GATHER_A)
       gs.stage(A, ga, zp, t * TN_BK, abuf(t));
     else
-      tn_stage(A, m0, M, lda, t * TN_BK, abuf(t));
-    tn_stage(B, n0, N, ldb, t * TN_BK, bbuf(t));
+      tn_stage_rows<256, 4>(A, m0, M, lda, t * TN_BK, abuf(t));
+    tn_stage_rows<256, 4>(B, n0, N, ldb, t * TN_BK, bbuf(t));
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -482,12 +305,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kshort(
       int gcol = n0 + seg * 8;
       if (grow < M && gcol + 8 <= N) {
         long crow = grow;
-        if (GATHER_A && ga.mode == 2) {
-          int n2, h2, w2;
-          np_decode(ga, (unsigned)grow, n2, h2, w2);
-          crow = ((long)n2 * ga.oH + h2 * ga.stride + ga.oqh) * ga.oW +
-                 w2 * ga.stride + ga.oqw;
-        }
+        if (GATHER_A && ga.mode == 2) crow = scatter_row(ga, grow);
         s16x8 v = *(const s16x8*)(ctile + row * 128 + seg * 8);
         if (direct_epi == 2)  // probe: nontemporal C stream
           __builtin_nontemporal_store(v, (s16x8*)(&C[crow * N + gcol]));
@@ -509,140 +327,11 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kshort(
         int row = m0 + wr * 64 + mi * 16 + fq * 4 + r;
         if (row >= M) continue;
         long crow = row;
-        if (GATHER_A && ga.mode == 2) {
-          int n2, h2, w2;
-          np_decode(ga, (unsigned)row, n2, h2, w2);
-          crow = ((long)n2 * ga.oH + h2 * ga.stride + ga.oqh) * ga.oW +
-                 w2 * ga.stride + ga.oqw;
-        }
+        if (GATHER_A && ga.mode == 2) crow = scatter_row(ga, row);
         C[crow * N + col] = f2bf(act_fwd(acc[mi][ni][r] + bv, act,
                                               slope));
       }
     }
-}
-
-// 256-row stager for the wide K-short tile (2048 chunks per 64-K tile)
-DEV_INLINE void tn_stage256(const unsigned short* __restrict__ g, int row0,
-                            int nrows, long ldk, int k0, char* lds) {
-  const int t = threadIdx.x;
-  const int wid = t >> 6;
-  #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    int chunk = i * 256 + t;
-    int row = chunk >> 3;
-    int slot = chunk & 7;
-    int gslot = slot ^ (row & 7);
-    int grow = min(row0 + row, nrows - 1);
-    const unsigned short* src = g + (long)grow * ldk + k0 + gslot * 8;
-    char* dst = lds + (i * 256 + wid * 64) * 16;
-    GLDS16(src, dst);
-  }
-}
-
-// Wide K=128 single-shot tile: 256(M) x 64(N), 4 waves each owning a
-// 64x64 panel, 2 blocks/CU (A 64 KiB + B 16 KiB LDS) — half the block
-// count of the 128x128 kshort at the same per-thread register budget,
-// so the per-block stage-latency chain amortizes over 2x the MACs.
-__global__ __launch_bounds__(256, 2) void gemm_tn_kshort_wide(
-    const unsigned short* __restrict__ A, const unsigned short* __restrict__ B,
-    unsigned short* __restrict__ C, const float* __restrict__ bias, int M,
-    int N, long lda, long ldb, int act, float slope) {
-  // 80 KiB dynamic LDS (static __shared__ caps at 64 KiB; the launcher
-  // raises MaxDynamicSharedMemorySize): 2 blocks/CU at exactly 160 KiB
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  auto abuf = [&](int t) -> char* { return lds + t * 32768; };       // 2x32K
-  auto bbuf = [&](int t) -> char* { return lds + 65536 + t * 8192; };
-
-  int nwgx = gridDim.x;
-  int bidx = blockIdx.x;
-  if (nwgx >= 8) {
-    int q = nwgx / 8, r = nwgx % 8;
-    int xcd = bidx % 8, idx = bidx / 8;
-    bidx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int m0 = bidx * 256;
-  const int n0 = blockIdx.y * 64;
-  const int wid = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int fr = lane & 15, fq = lane >> 4;
-
-  f32x4 acc[4][4];
-  #pragma unroll
-  for (int i = 0; i < 4; ++i)
-    #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
-
-  #pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    tn_stage256(A, m0, M, lda, t * 64, abuf(t));
-    // B: 64 rows x 64 k = 512 chunks (2 per thread)
-    const int th = threadIdx.x;
-    #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int chunk = i * 256 + th;
-      int row = chunk >> 3;
-      int slot = chunk & 7;
-      int gslot = slot ^ (row & 7);
-      int grow = min(n0 + row, N - 1);
-      const unsigned short* src = B + (long)grow * ldb + t * 64 + gslot * 8;
-      char* dst = bbuf(t) + (i * 256 + wid * 64) * 16;
-      GLDS16(src, dst);
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  #pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const char* Al = abuf(t);
-    const char* Bl = bbuf(t);
-    #pragma unroll
-    for (int kc = 0; kc < 2; ++kc) {
-      bf16x8 a[4], b[4];
-      #pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-        a[mi] = tn_frag(Al, wid * 64 + mi * 16 + fr, kc * 4 + fq);
-      #pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        b[ni] = tn_frag(Bl, ni * 16 + fr, kc * 4 + fq);
-      #pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-    }
-  }
-
-  // epilogue: ctile [256][64] bf16 = 32 KiB
-  unsigned short* ctile = (unsigned short*)lds;
-  __syncthreads();
-  #pragma unroll
-  for (int mi = 0; mi < 4; ++mi) {
-    #pragma unroll
-    for (int ni = 0; ni < 4; ++ni) {
-      int lc = ni * 16 + fr;
-      float bv = bias != nullptr ? bias[min(n0 + lc, N - 1)] : 0.f;
-      #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int lr = wid * 64 + mi * 16 + fq * 4 + r;
-        ctile[lr * 64 + lc] = f2bf(act_fwd(acc[mi][ni][r] + bv, act, slope));
-      }
-    }
-  }
-  __syncthreads();
-  const int t = threadIdx.x;
-  #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    int piece = i * 256 + t;  // 2048 pieces = 256 rows x 8 segs
-    int row = piece >> 3;
-    int seg = piece & 7;
-    int grow = m0 + row;
-    int gcol = n0 + seg * 8;
-    if (grow < M && gcol + 8 <= N)
-      *(s16x8*)(&C[(long)grow * N + gcol]) =
-          *(const s16x8*)(ctile + row * 64 + seg * 8);
-  }
 }
 
 // ---------------------------------------------------------------------------
@@ -657,40 +346,6 @@ constexpr int T2_BM = 256, T2_BN = 128, T2_BK = 64;
 constexpr int T2_AT = T2_BM * T2_BK * 2;  // 32 KiB
 constexpr int T2_BT = T2_BN * T2_BK * 2;  // 16 KiB
 
-DEV_INLINE void t2_stage_a(const unsigned short* __restrict__ g, int row0,
-                           int nrows, long ldk, int k0, char* lds) {
-  const int t = threadIdx.x;
-  const int wid = t >> 6;
-  #pragma unroll
-  for (int i = 0; i < 4; ++i) {           // 2048 chunks
-    int chunk = i * 512 + t;
-    int row = chunk >> 3;
-    int slot = chunk & 7;
-    int gslot = slot ^ (row & 7);
-    int grow = min(row0 + row, nrows - 1);
-    const unsigned short* src = g + (long)grow * ldk + k0 + gslot * 8;
-    char* dst = lds + (i * 512 + wid * 64) * 16;
-    GLDS16(src, dst);
-  }
-}
-
-DEV_INLINE void t2_stage_b(const unsigned short* __restrict__ g, int row0,
-                           int nrows, long ldk, int k0, char* lds) {
-  const int t = threadIdx.x;
-  const int wid = t >> 6;
-  #pragma unroll
-  for (int i = 0; i < 2; ++i) {           // 1024 chunks
-    int chunk = i * 512 + t;
-    int row = chunk >> 3;
-    int slot = chunk & 7;
-    int gslot = slot ^ (row & 7);
-    int grow = min(row0 + row, nrows - 1);
-    const unsigned short* src = g + (long)grow * ldk + k0 + gslot * 8;
-    char* dst = lds + (i * 512 + wid * 64) * 16;
-    GLDS16(src, dst);
-  }
-}
-
 template <bool GATHER_A>
 __global__ __launch_bounds__(512, 1) void gemm_tn_core256(
     const unsigned short* __restrict__ A, const unsigned short* __restrict__ B,
@@ -703,13 +358,8 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_core256(
     return lds + 2 * T2_AT + (i ? T2_BT : 0);
   };
 
-  int nwgx = gridDim.x;
-  int bidx = blockIdx.x;
-  if (nwgx >= 8) {
-    int q = nwgx / 8, r = nwgx % 8;
-    int xcd = bidx % 8, idx = bidx / 8;
-    bidx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int nwgx = gridDim.x;
+  const int bidx = xcd_remap(blockIdx.x, nwgx);
   const int m0 = bidx * T2_BM;
   const int n0 = blockIdx.y * T2_BN;
 
@@ -725,14 +375,14 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_core256(
     for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
   const int ntiles = K / T2_BK;
-  TnGatherStagerT<512> gs;
+  TnGatherStager<512, unsigned short> gs;
   if (GATHER_A) {
     gs.init(ga, m0, M);
     gs.stage(A, ga, zp, 0, abuf(0));
   } else {
-    t2_stage_a(A, m0, M, lda, 0, abuf(0));
+    tn_stage_rows<512, 4>(A, m0, M, lda, 0, abuf(0));
   }
-  t2_stage_b(B, n0, N, ldb, 0, bbuf(0));
+  tn_stage_rows<512, 2>(B, n0, N, ldb, 0, bbuf(0));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -742,8 +392,8 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_core256(
       if (GATHER_A)
         gs.stage(A, ga, zp, (t + 1) * T2_BK, abuf(cur ^ 1));
       else
-        t2_stage_a(A, m0, M, lda, (t + 1) * T2_BK, abuf(cur ^ 1));
-      t2_stage_b(B, n0, N, ldb, (t + 1) * T2_BK, bbuf(cur ^ 1));
+        tn_stage_rows<512, 4>(A, m0, M, lda, (t + 1) * T2_BK, abuf(cur ^ 1));
+      tn_stage_rows<512, 2>(B, n0, N, ldb, (t + 1) * T2_BK, bbuf(cur ^ 1));
     }
     const char* Al = abuf(cur);
     const char* Bl = bbuf(cur);
@@ -1050,6 +700,22 @@ __global__ __launch_bounds__(NT_THREADS, 2) void gemm_nt_core(
 }
 
 // ---------------------------------------------------------------------------
+// K-short launch for K in {64, 128}: picks the compile-time KT instantiation
+template <bool GATHER_A>
+static int launch_kshort(const void* A, const void* B, void* C,
+                         const float* bias, int M, int N, int K, long lda,
+                         long ldb, int act, float slope, int direct_epi,
+                         const ConvGather& ga, const void* zp, hipStream_t s) {
+  dim3 grid(ceil_div(M, TN_BM), ceil_div(N, TN_BN));
+  auto* kern = K == 64 ? gemm_tn_kshort<64, GATHER_A>
+                       : gemm_tn_kshort<128, GATHER_A>;
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, (const unsigned short*)A,
+                     (const unsigned short*)B, (unsigned short*)C, bias, M, N,
+                     lda, ldb, act, slope, direct_epi, ga,
+                     (const unsigned short*)zp);
+  return (int)grid.x;
+}
+
 extern "C" {
 
 // The 8-phase deep-pipelined 256x256 TN core (gemm8p.hip) is the default
@@ -1060,11 +726,9 @@ extern "C" {
 // GDLJ_TN256=1; requires bf16 output, no bn_part, gather mode != 2,
 // and enough rows to fill the chip at 1 block/CU.
 static int t2_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("GDLJ_TN256");
-    v = (e != nullptr && e[0] == '1') ? 1 : 0;
-    if (v) {
+  static const int v = [] {
+    int on = env_flag("GDLJ_TN256", 0);
+    if (on) {
       (void)hipFuncSetAttribute(
           reinterpret_cast<const void*>(&gemm_tn_core256<false>),
           hipFuncAttributeMaxDynamicSharedMemorySize, 2 * T2_AT + 2 * T2_BT);
@@ -1072,16 +736,13 @@ static int t2_enabled() {
           reinterpret_cast<const void*>(&gemm_tn_core256<true>),
           hipFuncAttributeMaxDynamicSharedMemorySize, 2 * T2_AT + 2 * T2_BT);
     }
-  }
+    return on;
+  }();
   return v;
 }
 
 static int kshort_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("GDLJ_KSHORT");
-    v = (e != nullptr && e[0] == '0') ? 0 : 1;
-  }
+  static const int v = env_flag("GDLJ_KSHORT", 1);
   return v;
 }
 
@@ -1090,48 +751,10 @@ int launch_gemm_tn(const void* A, const void* B, void* C_bf16, float* C_f32,
                    int act, float slope, float* bn_part, hipStream_t s) {
   if (C_bf16 != nullptr && bn_part == nullptr && (K == 64 || K == 128) &&
       kshort_enabled()) {
-    // 256x64 wide tile measured -10% vs the 128x128 kshort (fewer
-    // blocks did NOT amortize: the wide tile halves B-reuse per byte of
-    // LDS and the 80 KiB footprint stiffens scheduling) — opt-in probe.
-    static int kwide = -1;
-    if (kwide < 0) {
-      const char* e = getenv("GDLJ_KSHORT_WIDE");
-      kwide = (e != nullptr && e[0] == '1') ? 1 : 0;
-    }
-    if (kwide && K == 128 && (N & 63) == 0 && M >= 16 * 256) {
-      static int attr_done = 0;
-      if (!attr_done) {
-        (void)hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&gemm_tn_kshort_wide),
-            hipFuncAttributeMaxDynamicSharedMemorySize, 5 * 16384);
-        attr_done = 1;
-      }
-      dim3 gridw(ceil_div(M, 256), N / 64);
-      hipLaunchKernelGGL(gemm_tn_kshort_wide, gridw, dim3(256), 5 * 16384,
-                         s, (const unsigned short*)A,
-                         (const unsigned short*)B,
-                         (unsigned short*)C_bf16, bias, M, N, lda, ldb, act,
-                         slope);
-      return (int)gridw.x;
-    }
-    dim3 grid(ceil_div(M, TN_BM), ceil_div(N, TN_BN));
-    static int depi = -1;
-    if (depi < 0) {
-      const char* e = getenv("GDLJ_KSHORT_EPI");
-      depi = (e != nullptr && e[0] == '1') ? 1 : 0;  // probe: direct stores
-    }
-    ConvGather kdummy{};
-    if (K == 64)
-      hipLaunchKernelGGL((gemm_tn_kshort<64>), grid, dim3(256), 0, s,
-                         (const unsigned short*)A, (const unsigned short*)B,
-                         (unsigned short*)C_bf16, bias, M, N, lda, ldb, act,
-                         slope, depi, kdummy, nullptr);
-    else
-      hipLaunchKernelGGL((gemm_tn_kshort<128>), grid, dim3(256), 0, s,
-                         (const unsigned short*)A, (const unsigned short*)B,
-                         (unsigned short*)C_bf16, bias, M, N, lda, ldb, act,
-                         slope, depi, kdummy, nullptr);
-    return (int)grid.x;
+    // probe: direct stores instead of the LDS-staged epilogue
+    static const int depi = env_flag("GDLJ_KSHORT_EPI", 0);
+    return launch_kshort<false>(A, B, C_bf16, bias, M, N, K, lda, ldb, act,
+                                slope, depi, ConvGather{}, nullptr, s);
   }
   if (C_bf16 != nullptr && bn_part == nullptr &&
       gemm_tn_8p_eligible(M, N, K)) {
@@ -1159,11 +782,7 @@ int launch_gemm_tn(const void* A, const void* B, void* C_bf16, float* C_f32,
 }
 
 static int direct_conv_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("GDLJ_DIRECT_CONV");
-    v = (e != nullptr && e[0] == '0') ? 0 : 1;
-  }
+  static const int v = env_flag("GDLJ_DIRECT_CONV", 1);
   return v;
 }
 
@@ -1181,22 +800,9 @@ int launch_gemm_tn_gather(const void* img, const void* B, void* C_bf16,
                                 ga.W, ga.C, ga.Ho, ga.Wo, ga.R, ga.S,
                                 ga.stride, ga.pad, N, K, act, slope, s))
     return ceil_div(M, 128);
-  if (bn_part == nullptr && (K == 64 || K == 128) && kshort_enabled()) {
-    dim3 grid(ceil_div(M, TN_BM), ceil_div(N, TN_BN));
-    if (K == 64)
-      hipLaunchKernelGGL((gemm_tn_kshort<64, true>), grid, dim3(256), 0, s,
-                         (const unsigned short*)img,
-                         (const unsigned short*)B, (unsigned short*)C_bf16,
-                         bias, M, N, 0, ldb, act, slope, 0, ga,
-                         (const unsigned short*)zero_page);
-    else
-      hipLaunchKernelGGL((gemm_tn_kshort<128, true>), grid, dim3(256), 0, s,
-                         (const unsigned short*)img,
-                         (const unsigned short*)B, (unsigned short*)C_bf16,
-                         bias, M, N, 0, ldb, act, slope, 0, ga,
-                         (const unsigned short*)zero_page);
-    return (int)grid.x;
-  }
+  if (bn_part == nullptr && (K == 64 || K == 128) && kshort_enabled())
+    return launch_kshort<true>(img, B, C_bf16, bias, M, N, K, 0, ldb, act,
+                               slope, 0, ga, zero_page, s);
   if (bn_part == nullptr && gemm_tn_8p_eligible(M, N, K)) {
     return launch_gemm_tn_8p(img, B, C_bf16, bias, M, N, K, 0, ldb, act,
                              slope, 1, ga, zero_page, s);

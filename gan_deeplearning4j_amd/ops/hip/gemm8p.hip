@@ -53,15 +53,7 @@
 // Replaces the libnd4j/cuDNN GEMM-conv dependency surface of the reference
 // (SURVEY.md §2.2-2.3); no reference counterpart file exists.
 
-#include "common.h"
-#include <stdlib.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-
-#define GLDS16(gsrc, ldst)                                                    \
-  __builtin_amdgcn_global_load_lds(                                          \
-      (const __attribute__((address_space(1))) unsigned int*)(gsrc),          \
-      (__attribute__((address_space(3))) unsigned int*)(ldst), 16, 0, 0)
+#include "conv_gather.h"
 
 namespace p8 {
 
@@ -157,25 +149,7 @@ struct GatherA {
     for (int q = 0; q < 2; ++q) {
       int blk = ablk<BNT>(q, w);
       int np = min(m0 + blk * 16 + rsub, M - 1);
-      int n, ho, wo;
-      {
-        unsigned q1 = fdiv((unsigned)np, g.fWo);
-        wo = (int)((unsigned)np - q1 * g.Wo);
-        unsigned q2 = fdiv(q1, g.fHo);
-        ho = (int)(q1 - q2 * g.Ho);
-        n = (int)q2;
-      }
-      base[q] = (long)n * g.H * g.W * g.C;
-      if (g.mode == 0) {
-        h0[q] = ho * g.stride - g.pad;
-        w0[q] = wo * g.stride - g.pad;
-      } else if (g.mode == 2) {
-        h0[q] = ho + g.off_h;
-        w0[q] = wo + g.off_w;
-      } else {
-        h0[q] = ho + g.pad;
-        w0[q] = wo + g.pad;
-      }
+      gather_row_init(g, np, base[q], h0[q], w0[q]);
     }
   }
 
@@ -190,44 +164,8 @@ struct GatherA {
     #pragma unroll
     for (int i = 0; i < 2; ++i) {
       int k = k0 + i * 32 + ((pslot ^ swz<SWZ>(rsub)) << 3);
-      const unsigned short* src = zp;
-      if (k < g.rsc) {
-        int r, s, c;
-        {
-          unsigned rs = fdiv((unsigned)k, g.fC);
-          c = (int)((unsigned)k - rs * g.C);
-          unsigned rr = fdiv(rs, g.fS);
-          s = (int)(rs - rr * g.S);
-          r = (int)rr;
-        }
-        int hi, wi;
-        bool valid;
-        if (g.mode == 0) {
-          hi = h0[q] + r;
-          wi = w0[q] + s;
-          valid = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
-        } else if (g.mode == 2) {
-          hi = h0[q] - r;
-          wi = w0[q] - s;
-          valid = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
-        } else {
-          int hop = h0[q] - r;
-          int wop = w0[q] - s;
-          if (hop < 0 || wop < 0) {
-            valid = false;
-            hi = wi = 0;
-          } else {
-            unsigned qh = fdiv((unsigned)hop, g.fStride);
-            unsigned qw = fdiv((unsigned)wop, g.fStride);
-            valid = (hop == (int)(qh * g.stride)) &&
-                    (wop == (int)(qw * g.stride)) && (int)qh < g.H &&
-                    (int)qw < g.W;
-            hi = (int)qh;
-            wi = (int)qw;
-          }
-        }
-        if (valid) src = img + base[q] + (long)(hi * g.W + wi) * g.C + c;
-      }
+      const unsigned short* src =
+          gather_tap_src(img, g, zp, base[q], h0[q], w0[q], k);
       char* dst = op_lds + (((blk << 1) + i) << 10);
       GLDS16(src, dst);
     }
@@ -266,13 +204,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_8p(
   extern __shared__ __attribute__((aligned(16))) char lds[];
 
   // XCD-aware bijective remap over the whole grid (T1)
-  int nwg = gridDim.x * gridDim.y;
-  int bid = blockIdx.y * gridDim.x + blockIdx.x;
-  if (nwg >= 8) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = bid % 8, idx = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int nwg = gridDim.x * gridDim.y;
+  const int bid = xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, nwg);
   const int m0 = (TWEAK & 4) ? (bid / gridDim.y) * BM
                              : (bid % gridDim.x) * BM;
   const int n0 = (TWEAK & 4) ? (bid % gridDim.y) * BNT
@@ -457,16 +390,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_8p(
     int gcol = n0 + seg * 8;
     if (grow < M && gcol < N) {
       long crow = grow;
-      if (GATHER_A && ga.mode == 2) {
-        int n, h2, w2;
-        unsigned q1 = fdiv((unsigned)grow, ga.fWo);
-        w2 = (int)((unsigned)grow - q1 * ga.Wo);
-        unsigned q2 = fdiv(q1, ga.fHo);
-        h2 = (int)(q1 - q2 * ga.Ho);
-        n = (int)q2;
-        crow = ((long)n * ga.oH + h2 * ga.stride + ga.oqh) * ga.oW +
-               w2 * ga.stride + ga.oqw;
-      }
+      if (GATHER_A && ga.mode == 2) crow = scatter_row(ga, grow);
       s16x8 v = *(const s16x8*)(ctile + row * BNT + seg * 8);
       if (gcol + 8 <= N) {
         *(s16x8*)(&C[crow * N + gcol]) = v;
@@ -482,21 +406,12 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_8p(
 extern "C" {
 
 static int p8_swz_mode() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("GDLJ_8P_SWZ");
-    v = (e != nullptr) ? atoi(e) : 2;
-    if (v < 0 || v > 2) v = 2;
-  }
-  return v;
+  static const int e = env_int("GDLJ_8P_SWZ", 2);
+  return (e < 0 || e > 2) ? 2 : e;
 }
 
 static int p8_deep() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("GDLJ_8P_DEEP");
-    v = (e != nullptr && e[0] == '1') ? 1 : 0;
-  }
+  static const int v = env_flag("GDLJ_8P_DEEP", 0);
   return v;
 }
 
@@ -505,20 +420,14 @@ static int p8_deep() {
 // staging-latency-bound, so the tile shape doesn't matter and the
 // 2-block/CU 128-tile kernel's co-residency wins slightly.  Opt-in.
 static int p8_n128() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("GDLJ_8P_N128");
-    v = (e != nullptr && e[0] == '1') ? 1 : 0;
-  }
+  static const int v = env_flag("GDLJ_8P_N128", 0);
   return v;
 }
 
 static int p8_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("GDLJ_8P");
-    v = (e != nullptr && e[0] == '0') ? 0 : 1;
-    if (v) {
+  static const int v = [] {
+    int on = env_flag("GDLJ_8P", 1);
+    if (on) {
       // >64 KiB dynamic LDS needs an explicit opt-in per kernel
       #define P8_SETATTR(KF, B)                                              \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&KF),        \
@@ -538,7 +447,8 @@ static int p8_enabled() {
       P8_SETATTR((gemm_tn_8p<true, 2, false, 128, 2>), L128);
       #undef P8_SETATTR
     }
-  }
+    return on;
+  }();
   return v;
 }
 
@@ -550,11 +460,7 @@ static int p8_enabled() {
 // 812.8k -> 791.5k img/s; every shape the 8p wins on has M >= 131k).
 // GDLJ_8P_MINM overrides (0 for microbenches). profiles/gemm8p_ab.md.
 static int p8_min_m() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("GDLJ_8P_MINM");
-    v = (e != nullptr) ? atoi(e) : 32768;
-  }
+  static const int v = env_int("GDLJ_8P_MINM", 32768);
   return v;
 }
 

@@ -13,15 +13,9 @@
 //   - gather granularity of 16 channels per slot (C % 16 == 0).
 // See gemm8p.hip for the schedule derivation and correctness argument.
 
-#include "common.h"
-#include <stdlib.h>
+#include "conv_gather.h"
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
-
-#define GLDS16(gsrc, ldst)                                                    \
-  __builtin_amdgcn_global_load_lds(                                          \
-      (const __attribute__((address_space(1))) unsigned int*)(gsrc),          \
-      (__attribute__((address_space(3))) unsigned int*)(ldst), 16, 0, 0)
 
 namespace p8f {
 
@@ -71,21 +65,7 @@ struct GatherA {
     for (int q = 0; q < 2; ++q) {
       int blk = region_blk(q ? 0 : 2, w);
       int np = min(m0 + blk * 16 + rsub, M - 1);
-      unsigned q1 = fdiv((unsigned)np, g.fWo);
-      int wo = (int)((unsigned)np - q1 * g.Wo);
-      unsigned q2 = fdiv(q1, g.fHo);
-      int ho = (int)(q1 - q2 * g.Ho);
-      base[q] = (long)(int)q2 * g.H * g.W * g.C;
-      if (g.mode == 0) {
-        h0[q] = ho * g.stride - g.pad;
-        w0[q] = wo * g.stride - g.pad;
-      } else if (g.mode == 2) {
-        h0[q] = ho + g.off_h;
-        w0[q] = wo + g.off_w;
-      } else {
-        h0[q] = ho + g.pad;
-        w0[q] = wo + g.pad;
-      }
+      gather_row_init(g, np, base[q], h0[q], w0[q]);
     }
   }
 
@@ -100,44 +80,8 @@ struct GatherA {
     #pragma unroll
     for (int i = 0; i < 2; ++i) {
       int k = k0 + i * 64 + ((pslot ^ swz(rsub)) << 4);
-      const unsigned char* src = zp;
-      if (k < g.rsc) {
-        int r, s, c;
-        {
-          unsigned rs = fdiv((unsigned)k, g.fC);
-          c = (int)((unsigned)k - rs * g.C);
-          unsigned rr = fdiv(rs, g.fS);
-          s = (int)(rs - rr * g.S);
-          r = (int)rr;
-        }
-        int hi, wi;
-        bool valid;
-        if (g.mode == 0) {
-          hi = h0[q] + r;
-          wi = w0[q] + s;
-          valid = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
-        } else if (g.mode == 2) {
-          hi = h0[q] - r;
-          wi = w0[q] - s;
-          valid = hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
-        } else {
-          int hop = h0[q] - r;
-          int wop = w0[q] - s;
-          if (hop < 0 || wop < 0) {
-            valid = false;
-            hi = wi = 0;
-          } else {
-            unsigned qh = fdiv((unsigned)hop, g.fStride);
-            unsigned qw = fdiv((unsigned)wop, g.fStride);
-            valid = (hop == (int)(qh * g.stride)) &&
-                    (wop == (int)(qw * g.stride)) && (int)qh < g.H &&
-                    (int)qw < g.W;
-            hi = (int)qh;
-            wi = (int)qw;
-          }
-        }
-        if (valid) src = img + base[q] + (long)(hi * g.W + wi) * g.C + c;
-      }
+      const unsigned char* src =
+          gather_tap_src(img, g, zp, base[q], h0[q], w0[q], k);
       char* dst = op_lds + (((blk << 1) + i) << 10);
       GLDS16(src, dst);
     }
@@ -170,13 +114,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_8p_fp8(
   using namespace p8f;
   extern __shared__ __attribute__((aligned(16))) char lds[];
 
-  int nwg = gridDim.x * gridDim.y;
-  int bid = blockIdx.y * gridDim.x + blockIdx.x;
-  if (nwg >= 8) {
-    int q = nwg / 8, r = nwg % 8;
-    int xcd = bid % 8, idx = bid / 8;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int nwg = gridDim.x * gridDim.y;
+  const int bid = xcd_remap(blockIdx.y * gridDim.x + blockIdx.x, nwg);
   const int m0 = (bid % gridDim.x) * BM;
   const int n0 = (bid / gridDim.x) * BN;
 
@@ -310,16 +249,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_8p_fp8(
     int gcol = n0 + seg * 8;
     if (grow < M && gcol < N) {
       long crow = grow;
-      if (GATHER_A && ga.mode == 2) {
-        int n2, h2, w2;
-        unsigned q1 = fdiv((unsigned)grow, ga.fWo);
-        w2 = (int)((unsigned)grow - q1 * ga.Wo);
-        unsigned q2 = fdiv(q1, ga.fHo);
-        h2 = (int)(q1 - q2 * ga.Ho);
-        n2 = (int)q2;
-        crow = ((long)n2 * ga.oH + h2 * ga.stride + ga.oqh) * ga.oW +
-               w2 * ga.stride + ga.oqw;
-      }
+      if (GATHER_A && ga.mode == 2) crow = scatter_row(ga, grow);
       s16x8 v = *(const s16x8*)(ctile + row * 256 + seg * 8);
       if (gcol + 8 <= N) {
         *(s16x8*)(&C[crow * N + gcol]) = v;
@@ -335,11 +265,9 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_8p_fp8(
 extern "C" {
 
 static int p8f_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("GDLJ_8P_FP8");
-    v = (e != nullptr && e[0] == '0') ? 0 : 1;
-    if (v) {
+  static const int v = [] {
+    int on = env_flag("GDLJ_8P_FP8", 1);
+    if (on) {
       (void)hipFuncSetAttribute(
           reinterpret_cast<const void*>(&gemm_tn_8p_fp8<false>),
           hipFuncAttributeMaxDynamicSharedMemorySize, p8f::LDS_B);
@@ -347,7 +275,8 @@ static int p8f_enabled() {
           reinterpret_cast<const void*>(&gemm_tn_8p_fp8<true>),
           hipFuncAttributeMaxDynamicSharedMemorySize, p8f::LDS_B);
     }
-  }
+    return on;
+  }();
   return v;
 }
 
