@@ -22,7 +22,9 @@
 //            the stage for tile t+1 is issued before tile t's MFMAs),
 //            fragments read by ds_read_b64_tr_b16 (hardware transpose),
 //            split-K over blockIdx.z with fp32 atomics. Either operand may
-//            be gathered from an NHWC image (implicit wgrad).
+//            be gathered from an NHWC image (implicit wgrad).  Fallback
+//            of launch_gemm_nt: deep-K shapes with M, N >= 128 go to the
+//            256-wide deep-pipelined core in gemm8p_nt.hip.
 //
 // K must be a multiple of 64 for gemm_tn (callers pad; gathered A pads by
 // zero-page); gemm_nt handles arbitrary K by zero-fill.
@@ -828,6 +830,11 @@ int launch_gemm_tn_gather(const void* img, const void* B, void* C_bf16,
 void launch_gemm_nt(const void* A, const void* B, float* C, int M, int N,
                     int K, long lda, long ldb, int splitk, int gmode,
                     ConvGather gg, const void* zp, hipStream_t s) {
+  // the deep-pipelined 256-wide core (gemm8p_nt.hip) takes the shapes it
+  // wins on and re-derives split-K for its own tile count; gemm_nt_core
+  // below is the fallback and the A/B arm (GDLJ_NT8P=0)
+  if (launch_gemm_nt_8p(A, B, C, M, N, K, lda, ldb, splitk, gmode, gg, zp, s))
+    return;
   int kchunks = (K + NT_BK - 1) / NT_BK;
   if (splitk > kchunks) splitk = kchunks;
   int per_block = (kchunks + splitk - 1) / splitk;

@@ -152,6 +152,12 @@ int launch_gemm_tn_8p_tweak(int tweak, const void* A, const void* B, void* C,
                             int M, int N, int K, long lda, long ldb,
                             hipStream_t s);
 
+// gemm8p_nt.hip -- arguments as launch_gemm_nt; returns 1 and launches when
+// the shape is eligible (GDLJ_NT8P, GDLJ_NT8P_MINK), else 0.
+int launch_gemm_nt_8p(const void* A, const void* B, float* C, int M, int N,
+                      int K, long lda, long ldb, int splitk, int gmode,
+                      ConvGather gg, const void* zp, hipStream_t s);
+
 // fp8.hip -- e4m3 data is unsigned char; amax_bits holds a float's bits.
 void launch_amax(const void* x, long n, unsigned* amax_bits, hipStream_t s);
 void launch_fp8_make_scale(const unsigned* amax_bits, float* scale,
