@@ -31,6 +31,8 @@
 // conv_dgrad_direct_p (below) is the persistent class-fused variant of
 // the same arithmetic; the launchers try it first and keep this kernel
 // as the fallback and A/B arm (GDLJ_DGRAD_PERSIST=0).
+// conv_dgrad_direct_w (further below) is its one-block-per-CU variant for
+// the 8x8 class grid, tried before it (GDLJ_DGRAD_WIDE=0 skips it).
 
 #include <algorithm>
 #include <cstdlib>
@@ -706,7 +708,472 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
   }
 }
 
-// one-time dynamic-LDS opt-in for every instantiation of both kernels
+// ---------------------------------------------------------------------
+// Wide variant of the persistent kernel: ONE 8-wave block per CU.
+//
+// For the 8x8 class grid (conv3 dgrad / convT2 forward class).  A tile
+// is BM = 128 class pixels = the class grids of TWO images, times all of
+// C8 and all four parity classes out of one full-union region per image;
+// there is no qsplit.  Twice the pixels per W slice halves the W bytes
+// staged per output pixel, and the LDS of the whole CU pays for a third
+// W buffer: the slice TWO ahead is issued before the current one is
+// consumed, so a slice has two slice times to cross the L2.  (The
+// 16x16 class grid, one image per BM = 256 tile, was built and measured
+// slower than conv_dgrad_direct_p: profiles/dgrad_wide_ab.md.)
+//
+// The W stream is endless: the issue cursor walks (class, c-tile, slice)
+// cyclically and does not look at the tile, so every iteration issues
+// exactly two loads per thread and every counted wait is a constant.
+// The two slices issued past the block's last tile land in free buffers
+// and are drained before the block ends.
+//
+// A slice costs ONE barrier: wait for slice g, barrier, issue slice g+2
+// into the buffer of slice g-1 (every wave has read it: its LDS reads
+// are complete when it arrives at the barrier), fetch all fragments of
+// slice g, then its MFMAs, which run into the next slice's scalar work
+// and wait.
+//
+// Wait accounting (loads and stores retire in issue order).  Per thread
+// a slice is 2 loads, an epilogue ST = BM/64 dx stores, and with PACT
+// the y0 pieces of a (class, c-tile) are ST loads issued at its top,
+// under its whole slice loop.  At the wait of slice g the only newer
+// slice is g+1 (2); on the first slice after an epilogue also that
+// epilogue's stores and this c-tile's y0 loads; on the first slice of a
+// tile the region, which was issued after slice g+1 and must have
+// landed too, so there only the stores and the y0 loads may stay
+// outstanding.  A tile with an absent image (odd Nb) issues fewer
+// stores / y0 loads in some waves: it takes the counts without them,
+// which only waits for more.
+// The PACT counts hold only while the compiler leaves the y0 loads at
+// the top of the c-tile, ahead of its first slice wait: were they sunk
+// to their use in the epilogue, that wait would let slice g itself stay
+// outstanding.  The asm memory clobbers of the waits and barriers pin
+// them today; after a compiler change re-check in the .s that the
+// global_load_dwordx4 of y0 sit at the head of the c-tile loop
+// (profiles/dgrad_wide_ab.md lists what to look at).
+//
+// Wave tile: 32 px x 32 c (4 pixel groups x 2 channel halves), 4 MFMA
+// per kc against 4 ds_read_b128 (conv_dgrad_direct_p<1,..>: 4 against
+// 5).  Per output element the accumulation sequence
+// (tap, 128-co chunk, kc, one MFMA chain) and the epilogue expressions
+// are those of conv_dgrad_direct_p: dx / y are bit-identical to it; the
+// fp32 bias / BN partials are summed in another order.
+namespace cdd {
+constexpr int W_NBUF = 3;
+constexpr int W_THREADS = 512;
+constexpr int W_BM = 128;                // class pixels per tile
+constexpr int W_LDS_MAX = 160 * 1024;    // the whole LDS of a CU
+
+// one [64c][128co] W slice by the 512-thread block: 2 loads per thread,
+// same LDS image as two cdd_stage_w64 calls (k0 = 0, 64)
+DEV_INLINE void w_stage_slice(const unsigned short* __restrict__ g, long ldk,
+                              char* lds) {
+  const int t = threadIdx.x;
+  const int wid = t >> 6;
+  const int row = t >> 3;
+  const int gslot = (t & 7) ^ (row & 7);
+  const unsigned short* src = g + (long)row * ldk + gslot * 8;
+  GLDS16(src, lds + wid * 1024);
+  GLDS16(src + 64, lds + 8 * 1024 + wid * 1024);
+}
+
+template <int N>
+DEV_INLINE void w_wait_vm() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+}  // namespace cdd
+
+template <int NCT, bool PACT>
+__global__ __launch_bounds__(512, 1) void conv_dgrad_direct_w(
+    const unsigned short* __restrict__ dy,   // [N][Ho][Wo][Ko8]
+    const unsigned short* __restrict__ Wt,   // [R*S*C8][ldw], k = co
+    unsigned short* __restrict__ dx,         // [N][H][W][C8]
+    const unsigned short* __restrict__ y0,   // producer act out (or null)
+    float* __restrict__ part,                // [kPartRows][C8] f32 (or null)
+    const float* __restrict__ bias_fwd,      // convT fwd bias (or null)
+    float* __restrict__ stats_part,          // [kPartRows][2*C8] f32 (or null)
+    const unsigned short* __restrict__ zp,   // 16B zero page
+    int Nb, int H, int W, int C8, int Ho, int Wo, int Ko8, long ldw,
+    int R, int S, int pad, int act, float slope,
+    int Hc, int Wc, int rgn_rows, int rgn_cols, FastDiv fWc, int ntiles) {
+  using namespace cdd;
+  constexpr int MI = 2, NI = 2;       // wave tile: 32 px x 32 c
+  constexpr int WC = 4 / NI;          // waves across the 64 channels
+  constexpr int BM = W_BM;            // 4 pixel groups x 32 px
+  constexpr int ST = BM / 64;         // dx stores per thread per epilogue
+  constexpr int YL = PACT ? ST : 0;   // y0 loads per thread per c-tile
+  static_assert((8 / WC) * MI * 16 == BM && BM * 64 * 2 == WSLICE_B,
+                "wave tile; the ctile is one W buffer");
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  char* rgn = lds;                    // union dy regions, one per image
+
+  const int hwc = Hc * Wc;            // class pixels per image
+  const int imgs = BM / hwc;          // 2 (launcher)
+  const int cpi = rgn_rows * rgn_cols;          // region cells per image
+  const int rgn_img_b = cpi * Ko8 * 2;
+  const int rgn_b = imgs * rgn_img_b;
+  auto wbuf = [&](int i) -> char* { return lds + rgn_b + i * WSLICE_B; };
+
+  const int co_chunks = Ko8 >> 3;     // power of two (launcher)
+  const int cmask = co_chunks - 1;
+  const int csh = 31 - __builtin_clz(co_chunks);
+  const int ncell = imgs * cpi * co_chunks;
+  const int nj = Ko8 >> 7;            // 128-co chunks per tap
+
+  // union window over both parities, per axis
+  const int lo_w = min(p_boff(0, pad) - (p_ntap(0, pad, S) - 1),
+                       p_boff(1, pad) - (p_ntap(1, pad, S) - 1));
+  const int lo_h = min(p_boff(0, pad) - (p_ntap(0, pad, R) - 1),
+                       p_boff(1, pad) - (p_ntap(1, pad, R) - 1));
+
+  // ---- stage a tile's regions: [imgs][rgn_rows][rgn_cols][Ko8], zero
+  // halo, an image past Nb all zero; source-side chunk swizzle ----
+  auto stage_region = [&](int tile) {
+    const int n0 = tile * imgs;
+    for (int cell = threadIdx.x; cell < ncell; cell += W_THREADS) {
+      int rc_ = cell >> csh;
+      int slot = cell & cmask;
+      int img = rc_ >= cpi ? 1 : 0;
+      int rci = rc_ - img * cpi;
+      int rr = rci / rgn_cols;
+      int cc = rci - rr * rgn_cols;
+      int j = slot ^ (cc & cmask);
+      int hig = lo_h + rr;
+      int wig = lo_w + cc;
+      int n = n0 + img;
+      const unsigned short* src = zp;
+      if (n < Nb && hig >= 0 && hig < Ho && wig >= 0 && wig < Wo)
+        src = dy + (((long)n * Ho + hig) * Wo + wig) * Ko8 + j * 8;
+      char* dst = rgn + (cell & ~63) * 16;
+      GLDS16(src, dst);
+    }
+  };
+
+  // issue cursor of the endless W stream, in the consumer's order:
+  // class, c-tile, tap row, tap column, 128-co chunk (counters, no
+  // divisions: the slice loop's scalar work is on the critical path)
+  int i_cls = 0, i_ct = 0, i_rc = 0, i_sc = 0, i_j = 0;
+  auto issue_w = [&](int buf) {
+    const int qh = i_cls >> 1, qw = i_cls & 1;
+    const int tap = (p_tap0(qh, pad) + 2 * i_rc) * S + p_tap0(qw, pad) +
+                    2 * i_sc;
+    w_stage_slice(Wt + ((long)tap * C8 + i_ct * 64) * ldw + i_j * 128, ldw,
+                  wbuf(buf));
+    if (++i_j == nj) {
+      i_j = 0;
+      if (++i_sc == p_ntap(qw, pad, S)) {
+        i_sc = 0;
+        if (++i_rc == p_ntap(qh, pad, R)) {
+          i_rc = 0;
+          if (++i_ct == NCT) {
+            i_ct = 0;
+            i_cls = (i_cls + 1) & 3;
+          }
+        }
+      }
+    }
+  };
+
+  const int wid = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int pg = wid / WC;            // pixel group of this wave
+  const int ch = wid - pg * WC;       // channel part of this wave
+  const int wrow0 = pg * (MI * 16);   // first tile row of this wave
+
+  // this lane's A-side class pixels (a 16-pixel fragment never
+  // straddles two images: hwc is a multiple of 16)
+  int pxa[MI], pxh[MI], pxw[MI];
+  #pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    int pxl = wrow0 + mi * 16 + fr;
+    int img = pxl >= hwc ? 1 : 0;
+    int rem = pxl - img * hwc;
+    int hl = (int)fdiv((unsigned)rem, fWc);
+    pxa[mi] = img * rgn_img_b;
+    pxh[mi] = hl;
+    pxw[mi] = rem - hl * Wc;
+  }
+
+  const int t2 = threadIdx.x;
+  const int seg = t2 & 7;             // fixed c-block per thread
+  float bsum[NCT][8], ssum[NCT][8], ssq[NCT][8];
+  #pragma unroll
+  for (int k = 0; k < NCT; ++k)
+    #pragma unroll
+    for (int jj = 0; jj < 8; ++jj)
+      bsum[k][jj] = ssum[k][jj] = ssq[k][jj] = 0.f;
+
+  // convT-forward bias of this lane's columns, loaded and consumed ahead
+  // of every LDS-DMA load (see conv_dgrad_direct_p)
+  float biasv[NCT][NI];
+  #pragma unroll
+  for (int k = 0; k < NCT; ++k)
+    #pragma unroll
+    for (int ni = 0; ni < NI; ++ni) {
+      biasv[k][ni] = bias_fwd != nullptr
+                         ? bias_fwd[k * 64 + ch * (NI * 16) + ni * 16 + fr]
+                         : 0.f;
+      asm volatile("" : "+v"(biasv[k][ni]));
+    }
+
+  // this thread's epilogue pieces: piece e is row (e*512 + t2) >> 3 of
+  // the tile (e = image of the pair), 8 channels at seg
+  int erow[ST], eimg[ST], eoff[ST];
+  #pragma unroll
+  for (int e = 0; e < ST; ++e) {
+    int row = (e * W_THREADS + t2) >> 3;
+    int img = row >= hwc ? 1 : 0;
+    int rem = row - img * hwc;
+    int hl = (int)fdiv((unsigned)rem, fWc);
+    erow[e] = row;
+    eimg[e] = img;
+    eoff[e] = (2 * hl * W + 2 * (rem - hl * Wc)) * C8 + seg * 8;
+  }
+
+  // prologue: first region + the first two W slices; the first in-loop
+  // wait covers the region and slice 0
+  int tile = blockIdx.x;
+  stage_region(tile);
+  issue_w(0);
+  issue_w(1);
+
+  int cur = 0;                        // W buffer of the current slice
+  bool first_slice = true;
+  for (; tile < ntiles; tile += gridDim.x) {
+    const int n0 = tile * imgs;
+    const int ntile = tile + (int)gridDim.x;
+    const bool has_next = ntile < ntiles;
+    const bool tile_full = n0 + imgs <= Nb;
+
+    for (int cls = 0; cls < 4; ++cls) {
+      const int qh = cls >> 1, qw = cls & 1;
+      const int Rc = p_ntap(qh, pad, R), Sc = p_ntap(qw, pad, S);
+      const int rb0 = p_boff(qh, pad), wb0 = p_boff(qw, pad);
+
+      for (int ct = 0; ct < NCT; ++ct) {
+        const bool first_ct = cls == 0 && ct == 0;
+        const bool last_ct = cls == 3 && ct + 1 == NCT;
+
+        // output addresses of this thread's pieces; with PACT the
+        // producer's activation output is fetched now, under the whole
+        // slice loop of this c-tile
+        long eaddr[ST];
+        bool evalid[ST];
+        s16x8 yin[ST];
+        #pragma unroll
+        for (int e = 0; e < ST; ++e) {
+          int n = n0 + eimg[e];
+          evalid[e] = n < Nb;
+          eaddr[e] = ((long)n * H + qh) * W * C8 + (long)qw * C8 + eoff[e] +
+                     ct * 64;
+        }
+        if constexpr (PACT) {
+          #pragma unroll
+          for (int e = 0; e < ST; ++e) {
+            yin[e] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            if (evalid[e]) yin[e] = *(const s16x8*)(y0 + eaddr[e]);
+          }
+        }
+
+        f32x4 acc[MI][NI];
+        #pragma unroll
+        for (int i = 0; i < MI; ++i)
+          #pragma unroll
+          for (int j = 0; j < NI; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+
+        bool first_of_ct = true;
+        for (int rc_ = 0; rc_ < Rc; ++rc_)
+        for (int sc_ = 0; sc_ < Sc; ++sc_)
+        for (int j = 0; j < nj; ++j) {
+          // this slice has landed (counts: see the kernel's header)
+          if (!first_of_ct) {
+            w_wait_vm<2>();
+          } else if (!tile_full) {
+            if (first_ct && !first_slice) w_wait_vm<0>();
+            else w_wait_vm<2>();
+          } else if (first_slice) {
+            w_wait_vm<2 + YL>();
+          } else if (first_ct) {
+            w_wait_vm<ST + YL>();
+          } else {
+            w_wait_vm<2 + ST + YL>();
+          }
+          first_slice = false;
+          first_of_ct = false;
+          // the one barrier of a slice: every wave's part of this slice
+          // is in LDS, and every wave has finished reading the previous
+          // slice, whose buffer takes the slice two ahead
+          p_lds_barrier();
+          issue_w(cur == 0 ? 2 : cur - 1);
+          // region coordinates for this tap (always in-grid; halo
+          // cells are zero)
+          int abase[MI];
+          int axor[MI];
+          #pragma unroll
+          for (int mi = 0; mi < MI; ++mi) {
+            int rr = pxh[mi] + rb0 - rc_ - lo_h;
+            int cc = pxw[mi] + wb0 - sc_ - lo_w;
+            abase[mi] = pxa[mi] + (rr * rgn_cols + cc) * Ko8 * 2;
+            axor[mi] = cc & cmask;
+          }
+          const char* Wl = wbuf(cur);
+          // all fragments of the slice are fetched ahead of its MFMAs:
+          // fetched per kc, every kc step exposes an LDS round trip that
+          // two waves per SIMD cannot cover
+          bf16x8 a[4][MI], b[4][NI];
+          #pragma unroll
+          for (int kc = 0; kc < 4; ++kc) {
+            int jc = j * 16 + kc * 4 + fq;   // 16B co-chunk within Ko8
+            #pragma unroll
+            for (int mi = 0; mi < MI; ++mi)
+              a[kc][mi] = *(const bf16x8*)(rgn + abase[mi] +
+                                           ((jc ^ axor[mi]) << 4));
+            int sub = kc >> 1, kslot = (kc & 1) * 4 + fq;
+            #pragma unroll
+            for (int ni = 0; ni < NI; ++ni)
+              b[kc][ni] = cdd_wfrag(Wl + sub * 8 * 1024,
+                                    ch * (NI * 16) + ni * 16 + fr, kslot);
+          }
+          // keep the scheduler from sinking the reads back to their uses
+          __builtin_amdgcn_sched_barrier(0);
+          #pragma unroll
+          for (int kc = 0; kc < 4; ++kc)
+            #pragma unroll
+            for (int mi = 0; mi < MI; ++mi)
+              #pragma unroll
+              for (int ni = 0; ni < NI; ++ni)
+                acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    a[kc][mi], b[kc][ni], acc[mi][ni], 0, 0, 0);
+          cur = cur == 2 ? 0 : cur + 1;
+        }
+        // every wave is done with the last slice's W buffer (the ctile)
+        // and, on the tile's last c-tile, with the region
+        p_lds_barrier();
+
+        // the region is dead: put the next tile's region in flight under
+        // this epilogue; with PACT after the y0 pieces are taken (below),
+        // so that their wait does not cover it
+        if constexpr (!PACT) {
+          if (last_ct && has_next) stage_region(ntile);
+        }
+        asm volatile("" ::: "memory");
+
+        // ---- epilogue: ctile = the W buffer the last slice released
+        // (slices g+1, g+2 sit in the other two) ----
+        unsigned short* ctile =
+            (unsigned short*)wbuf(cur == 0 ? 2 : cur - 1);
+        #pragma unroll
+        for (int mi = 0; mi < MI; ++mi) {
+          #pragma unroll
+          for (int ni = 0; ni < NI; ++ni) {
+            int lc = ch * (NI * 16) + ni * 16 + fr;
+            float bv = 0.f;
+            #pragma unroll
+            for (int k = 0; k < NCT; ++k)
+              if (ct == k) bv = biasv[k][ni];
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              int lr = wrow0 + mi * 16 + fq * 4 + r;
+              float v = acc[mi][ni][r];
+              if (bias_fwd != nullptr) v = act_fwd(v + bv, act, slope);
+              ctile[lr * 64 + lc] = f2bf(v);
+            }
+          }
+        }
+        p_lds_barrier();
+        if constexpr (PACT) {
+          // Take the wait for the y0 pieces here, once.  The compiler
+          // cannot count the loads of the slice loop in between and
+          // waits for vmcnt(0), i.e. also for the two prefetched slices;
+          // loading y0 by inline asm with a counted wait here was tried,
+          // but the compiler copies the destination registers ahead of
+          // that wait.
+          #pragma unroll
+          for (int e = 0; e < ST; ++e) asm volatile("" : "+v"(yin[e]));
+          if (last_ct && has_next) stage_region(ntile);
+          asm volatile("" ::: "memory");
+        }
+        #pragma unroll
+        for (int e = 0; e < ST; ++e) {
+          if (!evalid[e]) continue;
+          const long addr = eaddr[e];
+          s16x8 v = *(const s16x8*)(ctile + erow[e] * 64 + seg * 8);
+          if constexpr (PACT) {
+            const s16x8 yv = yin[e];
+            #pragma unroll
+            for (int jj = 0; jj < 8; ++jj) {
+              float d = bf2f((unsigned short)v[jj]) *
+                        act_bwd_from_y(bf2f((unsigned short)yv[jj]), act,
+                                       slope);
+              v[jj] = (short)f2bf(d);
+              #pragma unroll
+              for (int k = 0; k < NCT; ++k)
+                if (ct == k) bsum[k][jj] += d;
+            }
+          }
+          if (stats_part != nullptr) {
+            #pragma unroll
+            for (int jj = 0; jj < 8; ++jj) {
+              float yv = bf2f((unsigned short)v[jj]);
+              #pragma unroll
+              for (int k = 0; k < NCT; ++k)
+                if (ct == k) {
+                  ssum[k][jj] += yv;
+                  ssq[k][jj] += yv * yv;
+                }
+            }
+          }
+          *(s16x8*)(dx + addr) = v;
+        }
+        // the ctile reads are complete before the next slice's barrier,
+        // behind which the buffer is restaged
+      }
+    }
+  }
+
+  // ---- once per block: drain the two slices issued past the last
+  // tile, then LDS tree + atomics over the register partials ----
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  float* red = (float*)rgn;
+  const int rrow = t2 >> 3;  // 64 contributor rows per seg
+  auto reduce_and_add = [&](const float* vec, float* dst) {
+    #pragma unroll
+    for (int jj = 0; jj < 8; ++jj)
+      red[(rrow * 8 + seg) * 8 + jj] = vec[jj];
+    __syncthreads();
+    for (int off = 32; off > 0; off >>= 1) {
+      if (rrow < off) {
+        #pragma unroll
+        for (int jj = 0; jj < 8; ++jj)
+          red[(rrow * 8 + seg) * 8 + jj] +=
+              red[((rrow + off) * 8 + seg) * 8 + jj];
+      }
+      __syncthreads();
+    }
+    if (rrow == 0) {
+      #pragma unroll
+      for (int jj = 0; jj < 8; ++jj)
+        atomicAdd(&dst[seg * 8 + jj], red[seg * 8 + jj]);
+    }
+    __syncthreads();  // red is reused by the next reduction
+  };
+  #pragma unroll
+  for (int k = 0; k < NCT; ++k) {
+    if (PACT && part != nullptr)
+      reduce_and_add(
+          bsum[k], part + (long)(blockIdx.x & (kPartRows - 1)) * C8 + k * 64);
+    if (stats_part != nullptr) {
+      float* srow =
+          stats_part + (long)(blockIdx.x & (kPartRows - 1)) * 2 * C8;
+      reduce_and_add(ssum[k], srow + k * 64);
+      reduce_and_add(ssq[k], srow + C8 + k * 64);
+    }
+  }
+}
+
+// one-time dynamic-LDS opt-in for every instantiation of the kernels
 static void cdd_set_attrs_once() {
   static int attr_done = 0;
   if (attr_done) return;
@@ -725,6 +1192,15 @@ static void cdd_set_attrs_once() {
   for (const void* f : fns)
     (void)hipFuncSetAttribute(
         f, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
+  const void* wide_fns[] = {
+      reinterpret_cast<const void*>(&conv_dgrad_direct_w<1, false>),
+      reinterpret_cast<const void*>(&conv_dgrad_direct_w<2, false>),
+      reinterpret_cast<const void*>(&conv_dgrad_direct_w<1, true>),
+      reinterpret_cast<const void*>(&conv_dgrad_direct_w<2, true>),
+  };
+  for (const void* f : wide_fns)
+    (void)hipFuncSetAttribute(
+        f, hipFuncAttributeMaxDynamicSharedMemorySize, cdd::W_LDS_MAX);
   attr_done = 1;
 }
 
@@ -776,6 +1252,31 @@ static DgradDirectPlan plan_persistent(int H, int W, int C8, int Ko8,
   return {};
 }
 
+// Wide kernel eligibility: the persistent kernel's conditions on strides,
+// channels, taps and parity; the 8x8 class grid, so that a tile is the
+// class grids of two images; and the tile's full-union regions +
+// three W buffers within the LDS of one CU.  Does not depend on the
+// batch: an odd image count ends in a half tile.
+static DgradDirectPlan plan_wide(int H, int W, int C8, int Ko8, long ldw,
+                                 int R, int S, int stride, int pad) {
+  if (stride != 2 || (C8 != 64 && C8 != 128) || Ko8 % 128 != 0 ||
+      (Ko8 & (Ko8 - 1)) != 0 || ldw != Ko8)
+    return {};
+  if (R < 2 || S < 2 || R > 8 || S > 8 || (H & 1) || (W & 1)) return {};
+  if (pad < 0) return {};
+  int Hc = H / 2, Wc = W / 2;
+  const int bm = W_BM;
+  // the square 8x8 class grid only: the other grids of 64 pixels are
+  // neither in the models nor tested
+  if (Hc != 8 || Wc != 8) return {};
+  int rgn_rows = p_axis_extent(Hc, pad, R, false);
+  int rgn_cols = p_axis_extent(Wc, pad, S, false);
+  int lds_b = (bm / (Hc * Wc)) * rgn_rows * rgn_cols * Ko8 * 2 +
+              W_NBUF * WSLICE_B;
+  if (lds_b > W_LDS_MAX) return {};
+  return DgradDirectPlan{2, bm, 0, lds_b, 1};
+}
+
 static DgradDirectPlan plan_oneshot(int H, int W, int C8, int Ko8, long ldw,
                                     int R, int S, int stride) {
   if (stride != 2 || C8 % 64 != 0 || Ko8 % 128 != 0 || ldw != Ko8)
@@ -797,6 +1298,19 @@ static DgradDirectPlan plan_oneshot(int H, int W, int C8, int Ko8, long ldw,
   return {};
 }
 
+static int device_cus() {
+  static int ncu = 0;
+  if (ncu == 0) {
+    int dev = 0, v = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount,
+                              dev) != hipSuccess || v <= 0)
+      v = 256;
+    ncu = v;
+  }
+  return ncu;
+}
+
 // Grid = CUs x 2 blocks (queried once), capped by the tile count and by
 // GDLJ_DGRAD_PERSIST_BLOCKS (re-read per call; lets small problems make
 // one block walk several tiles).
@@ -808,17 +1322,8 @@ static void launch_persistent(const DgradDirectArgs& a, DgradDirectPlan plan,
   int rgn_rows = p_axis_extent(rows_c, a.pad, a.R, qsplit != 0);
   int rgn_cols = p_axis_extent(Wc, a.pad, a.S, false);
   cdd_set_attrs_once();
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount,
-                              dev) != hipSuccess || v <= 0)
-      v = 256;
-    ncu = v;
-  }
   long ntiles = (long)a.Nb * Hc * Wc / bm * (qsplit ? 2 : 1);
-  long nblk = std::min<long>(ntiles, (long)ncu * 2);
+  long nblk = std::min<long>(ntiles, (long)device_cus() * 2);
   if (const char* e = getenv("GDLJ_DGRAD_PERSIST_BLOCKS")) {
     long cap = atol(e);
     if (cap > 0) nblk = std::min(nblk, cap);
@@ -845,6 +1350,44 @@ static void launch_persistent(const DgradDirectArgs& a, DgradDirectPlan plan,
   else CDD_P_LAUNCH(1, 2);
 #undef CDD_P_LAUNCH
 #undef CDD_P_LAUNCH2
+}
+
+// Grid = CUs x 1 blocks of 512 threads, capped like launch_persistent.
+static void launch_wide(const DgradDirectArgs& a, DgradDirectPlan plan,
+                        hipStream_t s) {
+  const int bm = plan.bm, lds_b = plan.lds_bytes;
+  int Hc = a.H / 2, Wc = a.W / 2;
+  int imgs = bm / (Hc * Wc);
+  int rgn_rows = p_axis_extent(Hc, a.pad, a.R, false);
+  int rgn_cols = p_axis_extent(Wc, a.pad, a.S, false);
+  cdd_set_attrs_once();
+  long ntiles = ((long)a.Nb + imgs - 1) / imgs;
+  long nblk = std::min<long>(ntiles, (long)device_cus());
+  if (const char* e = getenv("GDLJ_DGRAD_PERSIST_BLOCKS")) {
+    long cap = atol(e);
+    if (cap > 0) nblk = std::min(nblk, cap);
+  }
+  if (nblk <= 0) return;
+  dim3 grid((unsigned)nblk);
+#define CDD_W_LAUNCH2(NCT_, PACT_)                                          \
+  hipLaunchKernelGGL((conv_dgrad_direct_w<NCT_, PACT_>), grid,              \
+                     dim3(W_THREADS), lds_b, s,                             \
+                     (const unsigned short*)a.dy,                           \
+                     (const unsigned short*)a.Wt, (unsigned short*)a.dx,    \
+                     (const unsigned short*)a.y0, a.part, a.bias_fwd,       \
+                     a.stats_part, (const unsigned short*)a.zp, a.Nb, a.H,  \
+                     a.W, a.C8, a.Ho, a.Wo, a.Ko8, a.ldw, a.R, a.S, a.pad,  \
+                     a.act, a.slope, Hc, Wc, rgn_rows, rgn_cols,            \
+                     make_fastdiv(Wc), (int)ntiles)
+#define CDD_W_LAUNCH(NCT_)                                                  \
+  do {                                                                      \
+    if (a.y0 != nullptr) CDD_W_LAUNCH2(NCT_, true);                         \
+    else CDD_W_LAUNCH2(NCT_, false);                                        \
+  } while (0)
+  if (a.C8 == 64) CDD_W_LAUNCH(1);
+  else CDD_W_LAUNCH(2);
+#undef CDD_W_LAUNCH
+#undef CDD_W_LAUNCH2
 }
 
 static void launch_oneshot(const DgradDirectArgs& a, DgradDirectPlan plan,
@@ -876,15 +1419,28 @@ extern "C" {
 // GDLJ_DGRAD_PERSIST=0 routes the direct dgrad / convT forward to the
 // one-shot kernel instead of the persistent class-fused one (re-read
 // per call, like the other gates).
-int conv_dgrad_direct_persist_enabled() {
-  const char* e = getenv("GDLJ_DGRAD_PERSIST");
-  return !(e != nullptr && e[0] == '0' && e[1] == '\0');
+// GDLJ_DGRAD_WIDE=0 sends the geometries of the wide kernel back to the
+// two-blocks-per-CU persistent kernel (or, where that one does not take
+// them, to the caller's fallback).  The result is the plan's allow mask:
+// kDgradAllowPersist | kDgradAllowWide, or 0 for the one-shot kernel.
+int conv_dgrad_direct_allow() {
+  auto off = [](const char* name) {
+    const char* e = getenv(name);
+    return e != nullptr && e[0] == '0' && e[1] == '\0';
+  };
+  if (off("GDLJ_DGRAD_PERSIST")) return 0;
+  return off("GDLJ_DGRAD_WIDE") ? kDgradAllowPersist
+                                : kDgradAllowPersist | kDgradAllowWide;
 }
 
 DgradDirectPlan conv_dgrad_direct_plan(int H, int W, int C8, int Ko8,
                                        long ldw, int R, int S, int stride,
-                                       int pad, int allow_persist) {
-  if (allow_persist) {
+                                       int pad, int allow) {
+  if ((allow & kDgradAllowPersist) && (allow & kDgradAllowWide)) {
+    DgradDirectPlan p = cdd::plan_wide(H, W, C8, Ko8, ldw, R, S, stride, pad);
+    if (p.kind != 0) return p;
+  }
+  if (allow & kDgradAllowPersist) {
     DgradDirectPlan p =
         cdd::plan_persistent(H, W, C8, Ko8, ldw, R, S, stride, pad);
     if (p.kind != 0) return p;
@@ -894,7 +1450,8 @@ DgradDirectPlan conv_dgrad_direct_plan(int H, int W, int C8, int Ko8,
 
 void launch_conv_dgrad_direct(const DgradDirectArgs& a, DgradDirectPlan plan,
                               hipStream_t s) {
-  if (plan.kind == 2) cdd::launch_persistent(a, plan, s);
+  if (plan.kind == 2 && plan.wide) cdd::launch_wide(a, plan, s);
+  else if (plan.kind == 2) cdd::launch_persistent(a, plan, s);
   else if (plan.kind == 1) cdd::launch_oneshot(a, plan, s);
 }
 

@@ -311,7 +311,7 @@ DgradDirectArgs dgrad_direct_args(int64_t N, int64_t H, int64_t W, int64_t C8,
 DgradDirectPlan dgrad_direct_plan(const DgradDirectArgs& a, int64_t stride) {
   return conv_dgrad_direct_plan(a.H, a.W, a.C8, a.Ko8, a.ldw, a.R, a.S,
                                 (int)stride, a.pad,
-                                conv_dgrad_direct_persist_enabled());
+                                conv_dgrad_direct_allow());
 }
 
 // Direct parity-decomposed strided dgrad (conv_dgrad_direct.hip):
@@ -1032,12 +1032,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("conv_dgrad_direct_p_eligible",
           [](int64_t H, int64_t W, int64_t C8, int64_t Ko8, int64_t ldw,
              int64_t R, int64_t S, int64_t stride, int64_t pad) {
-            return conv_dgrad_direct_plan((int)H, (int)W, (int)C8, (int)Ko8,
-                                          (long)ldw, (int)R, (int)S,
-                                          (int)stride, (int)pad, 1)
-                       .kind == 2 ? 1 : 0;
+            DgradDirectPlan p = conv_dgrad_direct_plan(
+                (int)H, (int)W, (int)C8, (int)Ko8, (long)ldw, (int)R, (int)S,
+                (int)stride, (int)pad, kDgradAllowPersist | kDgradAllowWide);
+            return p.kind != 2 ? 0 : p.wide ? 2 : 1;
           },
-          "nonzero when the persistent direct dgrad takes this geometry");
+          "nonzero when a persistent direct dgrad takes this geometry "
+          "(2: the wide kernel)");
   mod.def("fused_adam", &fused_adam);
   mod.def("fused_rmsprop", &fused_rmsprop);
   mod.def("csv_load", &csv_load, "multithreaded CSV -> fp32 tensor");

@@ -97,11 +97,16 @@ inline ConvGather make_conv_gather(int N, int H, int W, int C, int Ho, int Wo,
 // ------------------------------------------- direct dgrad plan / arguments
 // Which direct strided dgrad kernel takes a geometry, and its tiling.
 struct DgradDirectPlan {
-  int kind;       // 0 ineligible, 1 one-shot kernel, 2 persistent kernel
-  int bm;         // class pixels per tile: 128 or 64
+  int kind;       // 0 ineligible, 1 one-shot kernel, 2 persistent kernels
+  int bm;         // class pixels per tile: 128 or 64 (wide: always 128)
   int qsplit;     // persistent only: 1 = tiles split by row parity
   int lds_bytes;  // dynamic LDS per block
+  int wide;       // kind 2: 1 = wide kernel, one 8-wave block per CU
 };
+
+// allow mask of conv_dgrad_direct_plan (wide needs persist as well)
+constexpr int kDgradAllowPersist = 1;
+constexpr int kDgradAllowWide = 2;
 
 // Arguments of the direct dgrad launch, named for the conv data-grad.  The
 // strided convT FORWARD runs the same kernel with the roles swapped: dy is
@@ -191,11 +196,13 @@ int launch_conv_direct_smallc(const void* img, const void* Wp, void* C,
                               int act, float slope, hipStream_t s);
 
 // conv_dgrad_direct.hip
-int conv_dgrad_direct_persist_enabled();  // GDLJ_DGRAD_PERSIST, read per call
-// Tries the persistent kernel (when allow_persist), then the one-shot one.
+// Allow mask from GDLJ_DGRAD_PERSIST / GDLJ_DGRAD_WIDE, read per call.
+int conv_dgrad_direct_allow();
+// Tries the wide, then the persistent kernel (as `allow` permits), then the
+// one-shot one.
 DgradDirectPlan conv_dgrad_direct_plan(int H, int W, int C8, int Ko8,
                                        long ldw, int R, int S, int stride,
-                                       int pad, int allow_persist);
+                                       int pad, int allow);
 void launch_conv_dgrad_direct(const DgradDirectArgs& a, DgradDirectPlan plan,
                               hipStream_t s);
 

@@ -1,12 +1,16 @@
-"""Per-shape A/B: dcol+col2im vs conv_dgrad_direct vs conv_dgrad_direct_p.
+"""Per-shape A/B of the strided dgrad / convT forward kernels.
 
-Three arms: "dcol" (GDLJ_DGRAD_DIRECT=0), "direct" (the one-shot direct
-kernel, GDLJ_DGRAD_PERSIST=0) and "persist" (the persistent class-fused
-kernel, the default).  Both gates are re-read per call, so all arms run
-in one process on identical data; the checksum of the result is compared
-across arms.  The dgrad rows time the full backward of a bias-free
-identity conv (dgrad + wgrad; wgrad identical in all arms), the convT
-rows time the forward alone.
+Four arms: "dcol" (GDLJ_DGRAD_DIRECT=0), "direct" (the one-shot direct
+kernel, GDLJ_DGRAD_PERSIST=0), "persist" (the two-blocks-per-CU persistent
+kernel, GDLJ_DGRAD_WIDE=0) and "wide" (the one-block-per-CU wide kernel,
+the default where eligible).  The gates are re-read per call, so all arms
+run in one process on identical data; the checksum of the result is
+compared across arms.  The persist arm is timed three times: the spread
+of those is the noise figure a wide time has to beat.  The dgrad rows
+time the full backward of a bias-free identity conv (dgrad + wgrad; wgrad
+identical in all arms), the convT rows time the forward alone.  Next to
+each row: the bytes the persist and wide kernels stage into LDS per call
+(plan arithmetic), for the DMA-rate column of the write-up.
 """
 import os
 import sys
@@ -19,7 +23,14 @@ from gan_deeplearning4j_amd.ops import gpu_ops  # noqa: E402
 ARMS = [
     ("dcol", {"GDLJ_DGRAD_DIRECT": "0"}),
     ("direct", {"GDLJ_DGRAD_DIRECT": "1", "GDLJ_DGRAD_PERSIST": "0"}),
-    ("persist", {"GDLJ_DGRAD_DIRECT": "1", "GDLJ_DGRAD_PERSIST": "1"}),
+    ("persist", {"GDLJ_DGRAD_DIRECT": "1", "GDLJ_DGRAD_PERSIST": "1",
+                 "GDLJ_DGRAD_WIDE": "0"}),
+    ("persist", {"GDLJ_DGRAD_DIRECT": "1", "GDLJ_DGRAD_PERSIST": "1",
+                 "GDLJ_DGRAD_WIDE": "0"}),
+    ("persist", {"GDLJ_DGRAD_DIRECT": "1", "GDLJ_DGRAD_PERSIST": "1",
+                 "GDLJ_DGRAD_WIDE": "0"}),
+    ("wide", {"GDLJ_DGRAD_DIRECT": "1", "GDLJ_DGRAD_PERSIST": "1",
+              "GDLJ_DGRAD_WIDE": "1"}),
 ]
 
 SHAPES = [
@@ -117,25 +128,87 @@ def bench_convt(nb, cin, hi, cout, r, stride, pad):
     return dt, out[0].float().abs().sum().item()
 
 
-def report(name, fn):
+def axis_window(pad, r, q):
+    t0 = (q + pad) & 1
+    nt = (r - t0 + 1) >> 1
+    bo = (q + pad - t0) >> 1
+    return bo - (nt - 1), bo
+
+
+def axis_extent(length, pad, r, qsplit=False):
+    (l0, h0), (l1, h1) = axis_window(pad, r, 0), axis_window(pad, r, 1)
+    if qsplit:
+        return length + max(h0 - l0, h1 - l1)
+    return length + max(h0, h1) - min(l0, l1)
+
+
+def staged_bytes(nb, h, c8, ko8, r, pad):
+    """(persist, wide) bytes staged into LDS per call: regions + W slices,
+    mirroring plan_persistent / plan_wide (None where not taken)."""
+    hc = wc = h // 2
+    nj = ko8 // 128
+    nct = c8 // 64
+    slices = sum(((r - ((qh + pad) & 1) + 1) >> 1) *
+                 ((r - ((qw + pad) & 1) + 1) >> 1)
+                 for qh in (0, 1) for qw in (0, 1)) * nj * nct
+    persist = None
+    for bm in (128, 64):
+        if wc > bm or bm % wc or (hc * wc) % bm:
+            continue
+        for qsplit in (0, 1):
+            rgn = (axis_extent(bm // wc, pad, r, bool(qsplit)) *
+                   axis_extent(wc, pad, r) * ko8 * 2)
+            if rgn + 32768 > 80 * 1024:
+                continue
+            tiles = nb * hc * wc // bm
+            persist = tiles * (rgn * (2 if qsplit else 1) + slices * 16384)
+            break
+        if persist is not None:
+            break
+    wide = None
+    if hc * wc == 64:
+        imgs = 2
+        rgn = imgs * axis_extent(hc, pad, r) * axis_extent(wc, pad, r) * ko8 * 2
+        if rgn + 3 * 16384 <= 160 * 1024:
+            tiles = (nb + imgs - 1) // imgs
+            wide = tiles * (rgn + slices * 16384)
+    return persist, wide
+
+
+def report(name, fn, geom=None):
     res = [(arm, *with_env(env, fn)) for arm, env in ARMS]
     c0 = res[0][2]
     ok = all(abs(c - c0) < 1e-3 * abs(c0) for _, _, c in res)
     match = "match" if ok else "MISMATCH " + " vs ".join(
         f"{c}" for _, _, c in res)
     times = " | ".join(f"{arm} {t:.3f} ms" for arm, t, _ in res)
-    print(f"{name}: {times} (persist/direct "
-          f"{res[2][1] / res[1][1]:.2f}x time) [{match}]", flush=True)
+    pt = [t for arm, t, _ in res if arm == "persist"]
+    wt = [t for arm, t, _ in res if arm == "wide"][0]
+    verdict = "WIDE WINS" if min(pt) - wt > max(pt) - min(pt) else "no win"
+    print(f"{name}: {times} (persist spread {max(pt) - min(pt):.3f} ms, "
+          f"wide - fastest persist {wt - min(pt):+.3f} ms: {verdict}) "
+          f"[{match}]", flush=True)
+    if geom is not None:
+        ps, ws = staged_bytes(*geom)
+        print(f"    staged per call: persist "
+              f"{'-' if ps is None else '%.2f GB' % (ps / 1e9)}, wide "
+              f"{'-' if ws is None else '%.2f GB' % (ws / 1e9)}", flush=True)
 
 
 if __name__ == "__main__":
+    # geom = (Nb, H, C8, Ko8, R, pad) in the kernel's dgrad naming
     for name, *args in SHAPES:
-        report(name, lambda: bench_one(*args))
+        nb, cin, h, cout, r, _, pad = args
+        report(name, lambda: bench_one(*args), (nb, h, cin, cout, r, pad))
     # the bench's real conv2 geometry (R=4 pad=1) with pact fusion
     for name, args in [
         ("conv2_r4_pact_bias", (16384, 64, 32, 128, 4, 2, 1, True)),
         ("conv2_r4_pact_nobias", (16384, 64, 32, 128, 4, 2, 1, False)),
     ]:
-        report(name, lambda: bench_pact(*args[:7], want_bias=args[7]))
+        nb, cin, h, cout, r, _, pad = args[:7]
+        report(name, lambda: bench_pact(*args[:7], want_bias=args[7]),
+               (nb, h, cin, cout, r, pad))
     for name, *args in CONVT_SHAPES:
-        report(name, lambda: bench_convt(*args))
+        nb, cin, hi, cout, r, _, pad = args
+        report(name, lambda: bench_convt(*args),
+               (nb, 2 * hi, cout, cin, r, pad))
