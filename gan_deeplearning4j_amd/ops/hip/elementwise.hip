@@ -221,10 +221,14 @@ __global__ void bce_logits_bwd(const unsigned short* __restrict__ logits,
 
 // Softmax cross-entropy vs one-hot (MCXENT; reference classifier head).
 // One wave per row (C <= a few thousand).
+// probs stay fp32 and everything is formed relative to the row maximum:
+// the backward subtracts the target from them, and a bf16 p (or an lse
+// rounded at the magnitude of the logits) loses the gradient p - y wherever
+// p is close to y.
 __global__ void softmax_xent_fwd(const unsigned short* __restrict__ logits,
                                  const unsigned short* __restrict__ onehot,
                                  float* __restrict__ loss_sum,
-                                 unsigned short* __restrict__ probs,
+                                 float* __restrict__ probs,
                                  int rows, int cols) {
   int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   int lane = threadIdx.x & 63;
@@ -238,25 +242,25 @@ __global__ void softmax_xent_fwd(const unsigned short* __restrict__ logits,
   for (int c = lane; c < cols; c += 64) se += __expf(bf2f(xr[c]) - mx);
   se = wave_reduce_sum(se);
   se = __shfl(se, 0, 64);
-  float lse = __logf(se) + mx;
+  float lsm = __logf(se);                 // lse - mx
   float l = 0.f;
   for (int c = lane; c < cols; c += 64) {
-    float p = __expf(bf2f(xr[c]) - lse);
-    probs[(long)row * cols + c] = f2bf(p);
-    l += bf2f(onehot[(long)row * cols + c]) * (lse - bf2f(xr[c]));
+    float xs = bf2f(xr[c]) - mx;
+    probs[(long)row * cols + c] = __expf(xs - lsm);
+    l += bf2f(onehot[(long)row * cols + c]) * (lsm - xs);
   }
   l = wave_reduce_sum(l);
   if (lane == 0) atomicAdd(loss_sum, l);
 }
 
 // dlogits = (probs - onehot) * gscale
-__global__ void softmax_xent_bwd(const unsigned short* __restrict__ probs,
+__global__ void softmax_xent_bwd(const float* __restrict__ probs,
                                  const unsigned short* __restrict__ onehot,
                                  unsigned short* __restrict__ dlogits,
                                  float gscale, long n) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i < n; i += (long)gridDim.x * blockDim.x)
-    dlogits[i] = f2bf((bf2f(probs[i]) - bf2f(onehot[i])) * gscale);
+    dlogits[i] = f2bf((probs[i] - bf2f(onehot[i])) * gscale);
 }
 
 // ------------------------------------------------------------- launchers
@@ -360,7 +364,7 @@ void launch_softmax_xent_fwd(const void* logits, const void* onehot,
   hipLaunchKernelGGL(softmax_xent_fwd, dim3(grid), dim3(wpb * 64), 0, s,
                      (const unsigned short*)logits,
                      (const unsigned short*)onehot, loss_sum,
-                     (unsigned short*)probs, rows, cols);
+                     (float*)probs, rows, cols);
 }
 
 void launch_softmax_xent_bwd(const void* probs, const void* onehot,
@@ -368,7 +372,7 @@ void launch_softmax_xent_bwd(const void* probs, const void* onehot,
                              hipStream_t s) {
   int grid = min(1024, ceil_div((int)min(n, (long)1 << 30), 256));
   hipLaunchKernelGGL(softmax_xent_bwd, dim3(grid), dim3(256), 0, s,
-                     (const unsigned short*)probs,
+                     (const float*)probs,
                      (const unsigned short*)onehot,
                      (unsigned short*)dlogits, gscale, n);
 }

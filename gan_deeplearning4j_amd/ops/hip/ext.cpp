@@ -634,7 +634,9 @@ std::vector<torch::Tensor> softmax_xent_fwd(torch::Tensor logits,
   check_bf16(onehot, "onehot");
   int64_t rows = logits.size(0), cols = logits.size(1);
   torch::Tensor s = torch::zeros({1}, logits.options().dtype(torch::kFloat32));
-  torch::Tensor probs = torch::empty_like(logits);
+  // fp32: the backward subtracts the target from them
+  torch::Tensor probs =
+      torch::empty_like(logits, logits.options().dtype(torch::kFloat32));
   launch_softmax_xent_fwd(logits.data_ptr(), onehot.data_ptr(),
                           s.data_ptr<float>(), probs.data_ptr(), (int)rows,
                           (int)cols, cur_stream());
@@ -643,8 +645,11 @@ std::vector<torch::Tensor> softmax_xent_fwd(torch::Tensor logits,
 
 torch::Tensor softmax_xent_bwd(torch::Tensor probs, torch::Tensor onehot,
                                double gscale) {
-  check_bf16(probs, "probs");
-  torch::Tensor d = torch::empty_like(probs);
+  check_f32(probs, "probs");
+  check_bf16(onehot, "onehot");
+  TORCH_CHECK(onehot.numel() == probs.numel(), "onehot shape");
+  torch::Tensor d =
+      torch::empty_like(probs, probs.options().dtype(torch::kBFloat16));
   launch_softmax_xent_bwd(probs.data_ptr(), onehot.data_ptr(), d.data_ptr(),
                           (float)gscale, probs.numel(), cur_stream());
   return d;

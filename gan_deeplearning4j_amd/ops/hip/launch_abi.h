@@ -245,6 +245,8 @@ void launch_bce_fwd(const void* logits, const void* labels, float* loss_sum,
                     long n, hipStream_t s);
 void launch_bce_bwd(const void* logits, const void* labels, void* dlogits,
                     float gscale, long n, hipStream_t s);
+// probs is fp32 [rows][cols] (the backward subtracts the target from it);
+// logits, onehot and dlogits are bf16.
 void launch_softmax_xent_fwd(const void* logits, const void* onehot,
                              float* loss_sum, void* probs, int rows, int cols,
                              hipStream_t s);

@@ -25,6 +25,10 @@ def mk(shape, seed=0, scale=1.0):
     return t.to(DEV, torch.bfloat16)
 
 
+# relerr is one number for the whole tensor, normalised by its maximum: fine
+# for a GEMM, blind to a wrong memory-bound kernel (an Adam that does nothing
+# passes at 0.02).  New tests for batchnorm / elementwise / pool / optim
+# kernels belong in test_membound_gpu.py, on membound_oracle's comparators.
 def relerr(a, b):
     a = a.float().cpu()
     b = b.float().cpu()
