@@ -56,6 +56,9 @@ class ModelConfig:
     #                                keep is 1 - dis_dropout)
     dis_input_noise_std: float = 0.0  # stddev of Gaussian "instance"
     #                                noise on D's input (0 = none)
+    dis_spectral_norm: bool = False  # spectral normalization on every D
+    #                                weight layer; also drops D's BatchNorm
+    #                                (the SNGAN recipe)
 
     def validate_regularisers(self) -> None:
         if not 0.0 <= self.dis_dropout < 1.0:

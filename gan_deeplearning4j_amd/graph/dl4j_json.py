@@ -111,6 +111,10 @@ def _layer_to_dl4j(graph: ComputationGraph, name: str,
     lr = getattr(layer, "lr", None)
     base = _base_layer_fields(graph, name, lr)
     base["idropout"] = idropout
+    if getattr(layer, "spectral_norm", False):
+        # framework extension field (DL4J has no spectral norm); emitted
+        # only when set, read back by _layer_from_dl4j
+        base["spectralNorm"] = True
     if t in ("DropoutLayer", "GaussianNoiseLayer"):
         base["idropout"] = _idropout_to_dl4j(layer)
         return {"@class": _NS_L + "DropoutLayer", **base,
@@ -295,15 +299,17 @@ def _layer_from_dl4j(ld: dict):
     if isinstance(iu, dict):
         lr = iu.get("learningRate")
     act = _act_from(ld.get("activationFn"))
+    sn = bool(ld.get("spectralNorm", False))
     if cls == "DenseLayer":
-        return L.DenseLayer(ld["nin"], ld["nout"], act, lr)
+        return L.DenseLayer(ld["nin"], ld["nout"], act, lr, spectral_norm=sn)
     if cls == "OutputLayer":
         loss = _LOSS_FROM_DL4J.get(_cls(ld.get("lossFn", {})), "xent")
-        return L.OutputLayer(ld["nin"], ld["nout"], act, loss, lr)
+        return L.OutputLayer(ld["nin"], ld["nout"], act, loss, lr,
+                             spectral_norm=sn)
     if cls == "ConvolutionLayer":
         return L.Conv2dLayer(ld["nin"], ld["nout"], ld["kernelSize"][0],
                              ld["stride"][0], ld.get("padding", [0])[0],
-                             act, lr)
+                             act, lr, spectral_norm=sn)
     if cls == "Deconvolution2D":
         return L.ConvTranspose2dLayer(ld["nin"], ld["nout"],
                                       ld["kernelSize"][0], ld["stride"][0],

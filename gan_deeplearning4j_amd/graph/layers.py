@@ -9,6 +9,11 @@ Each layer carries DL4J-style metadata: a per-layer learning rate override
 (`lr`), frozen flag, and a param table keyed by DL4J names
 ('W', 'b', 'gamma', 'beta', 'mean', 'var') used by the weight-sync blocks
 (reference Java:429-460, 474-510, 516-542).
+
+Dense, Output and Conv2d layers take `spectral_norm=True` (a framework
+extension, torch.nn.utils.spectral_norm semantics): forward then runs on
+W / sigma from ops.functional.spectral_normalize, while get_param/set_param
+and the optimizer keep addressing the raw W.
 """
 
 from __future__ import annotations
@@ -37,6 +42,43 @@ class BaseLayer(nn.Module):
         # a BatchNorm over the same feature axis: the producer's GPU kernel
         # then also emits the BN batch statistics (skips one full pass)
         self.emit_bn_stats: bool = False
+        # spectral normalization (Dense/Output/Conv2d, `spectral_norm=True`):
+        # the power-iteration vectors are PLAIN fp32 tensor attributes, for
+        # the reasons _StochasticLayer documents for its state - moved by
+        # _apply, never cast to the compute dtype, mutated in place only,
+        # neither parameters nor buffers (n_params() is unchanged)
+        self.spectral_norm: bool = False
+        self.sn_u: Optional[torch.Tensor] = None
+        self.sn_v: Optional[torch.Tensor] = None
+
+    # -- spectral norm plumbing (no-ops unless the layer sets the flag)
+    def _init_spectral(self, flag: bool, rows: int, cols: int) -> None:
+        self.spectral_norm = bool(flag)
+        if self.spectral_norm:
+            self.sn_u = torch.zeros(rows)
+            self.sn_v = torch.zeros(cols)
+
+    def _reset_spectral(self, gen: torch.Generator) -> None:
+        """u, v ~ N(0, 1) normalised, as torch.nn.utils.spectral_norm draws
+        them; from the graph's generator, and only when the flag is set, so
+        a layer without it leaves every existing initialisation as it was."""
+        if not self.spectral_norm:
+            return
+        for t in (self.sn_u, self.sn_v):
+            fresh = torch.randn(t.numel(), generator=gen)
+            t.copy_(torch.nn.functional.normalize(fresh, dim=0, eps=1e-12))
+
+    def _sn_weight(self, w: torch.Tensor) -> torch.Tensor:
+        if not self.spectral_norm:
+            return w
+        return OF.spectral_normalize(w, self.sn_u, self.sn_v, self.training)
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        if self.sn_u is not None:
+            self.sn_u = fn(self.sn_u).to(torch.float32)
+            self.sn_v = fn(self.sn_v).to(torch.float32)
+        return self
 
     # -- DL4J-style param access (getParam/setParam, reference Java:431-459)
     def get_param(self, key: str) -> torch.Tensor:
@@ -94,23 +136,26 @@ class DenseLayer(BaseLayer):
     PARAM_KEYS = {"W": "weight", "b": "bias"}
 
     def __init__(self, n_in: int, n_out: int, activation: str = "identity",
-                 lr=None, frozen=False, bias: bool = True, slope: float = 0.2):
+                 lr=None, frozen=False, bias: bool = True, slope: float = 0.2,
+                 spectral_norm: bool = False):
         super().__init__(lr, frozen)
         self.n_in, self.n_out = n_in, n_out
         self.activation = activation
         self.slope = slope
         self.weight = nn.Parameter(torch.empty(n_out, n_in))
         self.bias = nn.Parameter(torch.zeros(n_out)) if bias else None
+        self._init_spectral(spectral_norm, n_out, n_in)
 
     def reset_parameters(self, gen: torch.Generator):
         xavier_(self.weight, self.n_in, self.n_out, gen)
         if self.bias is not None:
             with torch.no_grad():
                 self.bias.zero_()
+        self._reset_spectral(gen)
 
     def forward(self, x):
-        return OF.linear(x, self.weight, self.bias, self.activation,
-                         self.slope,
+        return OF.linear(x, self._sn_weight(self.weight), self.bias,
+                         self.activation, self.slope,
                          emit_stats=self.emit_bn_stats and self.training)
 
     def out_shape(self, in_shape):
@@ -125,14 +170,16 @@ class OutputLayer(DenseLayer):
     """
 
     def __init__(self, n_in: int, n_out: int, activation: str, loss: str,
-                 lr=None, frozen=False):
-        super().__init__(n_in, n_out, "identity", lr, frozen)
+                 lr=None, frozen=False, spectral_norm: bool = False):
+        super().__init__(n_in, n_out, "identity", lr, frozen,
+                         spectral_norm=spectral_norm)
         self.inference_activation = activation
         self.loss = loss
 
     def forward(self, x):
         # logits; activation applied by ComputationGraph.output()
-        return OF.linear(x, self.weight, self.bias, "identity")
+        return OF.linear(x, self._sn_weight(self.weight), self.bias,
+                         "identity")
 
 
 class Conv2dLayer(BaseLayer):
@@ -140,7 +187,8 @@ class Conv2dLayer(BaseLayer):
 
     def __init__(self, c_in: int, c_out: int, kernel: int, stride: int = 1,
                  padding: int = 0, activation: str = "identity",
-                 lr=None, frozen=False, slope: float = 0.2):
+                 lr=None, frozen=False, slope: float = 0.2,
+                 spectral_norm: bool = False):
         super().__init__(lr, frozen)
         self.c_in, self.c_out = c_in, c_out
         self.kernel, self.stride, self.padding = kernel, stride, padding
@@ -148,16 +196,20 @@ class Conv2dLayer(BaseLayer):
         self.slope = slope
         self.weight = nn.Parameter(torch.empty(c_out, c_in, kernel, kernel))
         self.bias = nn.Parameter(torch.zeros(c_out))
+        # matrix view [c_out, c_in * k * k] (torch's dim=0)
+        self._init_spectral(spectral_norm, c_out, c_in * kernel * kernel)
 
     def reset_parameters(self, gen: torch.Generator):
         k2 = self.kernel * self.kernel
         xavier_(self.weight, self.c_in * k2, self.c_out * k2, gen)
         with torch.no_grad():
             self.bias.zero_()
+        self._reset_spectral(gen)
 
     def forward(self, x):
-        return OF.conv2d(x, self.weight, self.bias, self.stride, self.padding,
-                         self.activation, self.slope,
+        return OF.conv2d(x, self._sn_weight(self.weight), self.bias,
+                         self.stride, self.padding, self.activation,
+                         self.slope,
                          emit_stats=self.emit_bn_stats and self.training,
                          prev_act=getattr(self, "prev_act", None))
 
@@ -173,8 +225,17 @@ class ConvTranspose2dLayer(BaseLayer):
 
     def __init__(self, c_in: int, c_out: int, kernel: int, stride: int = 1,
                  padding: int = 0, activation: str = "identity",
-                 lr=None, frozen=False, slope: float = 0.2):
+                 lr=None, frozen=False, slope: float = 0.2,
+                 spectral_norm: bool = False):
         super().__init__(lr, frozen)
+        if spectral_norm:
+            # the matrix view of a transposed-conv weight is a permutation
+            # of [in, out, kh, kw]; generator-side spectral norm is not
+            # implemented
+            raise ValueError(
+                "ConvTranspose2dLayer does not support spectral_norm=True "
+                "(spectral normalization covers Dense, Output and Conv2d "
+                "layers only)")
         self.c_in, self.c_out = c_in, c_out
         self.kernel, self.stride, self.padding = kernel, stride, padding
         self.activation = activation

@@ -7,6 +7,11 @@ The zip layout:
     coefficients.bin    - flattened fp32 parameter vector in layer order
                           (per layer: W, b, gamma, beta, mean, var)
     updaterState.bin    - flattened fp32 updater state (saveUpdater=true)
+    spectralNorm.bin    - framework extension, present ONLY when some layer
+                          has spectral_norm=True: the fp32 power-iteration
+                          vectors, per flagged layer in layer order, u then
+                          v (eval-mode sigma depends on them, so they travel
+                          with the model)
 
 DL4J-compat scope (VERDICT round-1 item 5, documented delta):
 configuration.json is emitted in DL4J 1.0.0-beta3's Jackson layout
@@ -38,10 +43,12 @@ from . import layers as L
 from .builder import ComputationGraph, GraphBuilder, InputType
 
 _LAYER_FIELDS = {
-    "DenseLayer": ("n_in", "n_out", "activation", "lr", "frozen", "slope"),
-    "OutputLayer": ("n_in", "n_out", "inference_activation", "loss", "lr", "frozen"),
+    "DenseLayer": ("n_in", "n_out", "activation", "lr", "frozen", "slope",
+                   "spectral_norm"),
+    "OutputLayer": ("n_in", "n_out", "inference_activation", "loss", "lr",
+                    "frozen", "spectral_norm"),
     "Conv2dLayer": ("c_in", "c_out", "kernel", "stride", "padding", "activation",
-                    "lr", "frozen", "slope"),
+                    "lr", "frozen", "slope", "spectral_norm"),
     "ConvTranspose2dLayer": ("c_in", "c_out", "kernel", "stride", "padding",
                              "activation", "lr", "frozen", "slope"),
     "BatchNormLayer": ("num_features", "eps", "momentum", "lr", "frozen"),
@@ -70,15 +77,21 @@ def _folded(layer, d: dict):
 _CTOR_ARGS = {
     "DenseLayer": lambda d: L.DenseLayer(d["n_in"], d["n_out"], d["activation"],
                                          d.get("lr"), d.get("frozen", False),
-                                         slope=d.get("slope", 0.2)),
+                                         slope=d.get("slope", 0.2),
+                                         spectral_norm=d.get("spectral_norm",
+                                                             False)),
     "OutputLayer": lambda d: L.OutputLayer(d["n_in"], d["n_out"],
                                            d["inference_activation"], d["loss"],
-                                           d.get("lr"), d.get("frozen", False)),
+                                           d.get("lr"), d.get("frozen", False),
+                                           spectral_norm=d.get("spectral_norm",
+                                                               False)),
     "Conv2dLayer": lambda d: L.Conv2dLayer(d["c_in"], d["c_out"], d["kernel"],
                                            d["stride"], d["padding"],
                                            d["activation"], d.get("lr"),
                                            d.get("frozen", False),
-                                           slope=d.get("slope", 0.2)),
+                                           slope=d.get("slope", 0.2),
+                                           spectral_norm=d.get("spectral_norm",
+                                                               False)),
     "ConvTranspose2dLayer": lambda d: L.ConvTranspose2dLayer(
         d["c_in"], d["c_out"], d["kernel"], d["stride"], d["padding"],
         d["activation"], d.get("lr"), d.get("frozen", False),
@@ -110,12 +123,43 @@ def _layer_to_dict(layer: L.BaseLayer) -> dict:
     d = {"type": tname}
     for f in _LAYER_FIELDS[tname]:
         v = getattr(layer, f)
+        if f == "spectral_norm" and not v:
+            continue  # emitted only when set: existing JSON stays as it is
         d[f] = list(v) if isinstance(v, tuple) else v
     return d
 
 
 def _layer_from_dict(d: dict) -> L.BaseLayer:
     return _CTOR_ARGS[d["type"]](d)
+
+
+def spectral_layers(graph: ComputationGraph) -> list:
+    """(name, layer) of every layer with spectral_norm=True, layer order."""
+    return [(n, graph.layers[n]) for n in graph.layer_names()
+            if getattr(graph.layers[n], "spectral_norm", False)]
+
+
+def spectral_state_flat(graph: ComputationGraph) -> torch.Tensor:
+    """fp32 u then v of every flagged layer, concatenated in layer order."""
+    chunks = []
+    for _, layer in spectral_layers(graph):
+        chunks += [layer.sn_u.detach().float().cpu().reshape(-1),
+                   layer.sn_v.detach().float().cpu().reshape(-1)]
+    return torch.cat(chunks) if chunks else torch.empty(0)
+
+
+def load_spectral_state_flat(graph: ComputationGraph,
+                             vec: torch.Tensor) -> None:
+    """Inverse of spectral_state_flat; copies IN PLACE."""
+    off = 0
+    for _, layer in spectral_layers(graph):
+        for t in (layer.sn_u, layer.sn_v):
+            n = t.numel()
+            t.copy_(vec[off:off + n].to(t.device))
+            off += n
+    if off != vec.numel():
+        raise ValueError(
+            f"spectral state size mismatch: used {off}, got {vec.numel()}")
 
 
 def graph_config_dict(graph: ComputationGraph) -> dict:
@@ -198,6 +242,9 @@ class ModelSerializer:
                 json.dumps(graph_config_dict(graph), indent=1),
             )
             zf.writestr("coefficients.bin", params.tobytes())
+            if spectral_layers(graph):
+                zf.writestr("spectralNorm.bin", spectral_state_flat(
+                    graph).numpy().astype("<f4").tobytes())
             if save_updater and graph._updater is not None:
                 sd = graph.updater.state_dict()
                 chunks = []
@@ -251,6 +298,17 @@ class ModelSerializer:
             )
             graph.load_params_flat(vec)
             graph._initialized = True
+            if spectral_layers(graph):
+                if "spectralNorm.bin" in names:
+                    load_spectral_state_flat(graph, torch.from_numpy(
+                        np.frombuffer(zf.read("spectralNorm.bin"),
+                                      dtype="<f4").copy()))
+                else:
+                    # a zip without the vectors (written elsewhere): draw
+                    # them as init() would, from the graph's seed
+                    gen = torch.Generator().manual_seed(graph.seed)
+                    for _, layer in spectral_layers(graph):
+                        layer._reset_spectral(gen)
             if load_updater and "updater.json" in zf.namelist():
                 meta = json.loads(zf.read("updater.json"))
                 flat = np.frombuffer(
@@ -286,6 +344,8 @@ class ModelSerializer:
                 "updater": (
                     graph.updater.state_dict() if graph._updater else None
                 ),
+                **({"spectral": spectral_state_flat(graph)}
+                   if spectral_layers(graph) else {}),
             },
             path,
         )
@@ -297,6 +357,8 @@ class ModelSerializer:
         graph = graph_from_config_dict(blob["config"])
         graph.load_state_dict(blob["state_dict"])
         graph._initialized = True
+        if blob.get("spectral") is not None:
+            load_spectral_state_flat(graph, blob["spectral"])
         if blob.get("updater") is not None:
             graph.updater.load_state_dict(blob["updater"])
         return graph

@@ -64,10 +64,16 @@ def _dis_graph(cfg: GanConfig, stages: list[int], s_last: int) -> ComputationGra
 
     model.dis_dropout > 0 adds a DropoutLayer after every conv stage and
     after d_dense_feat; model.dis_input_noise_std > 0 adds Gaussian noise
-    on the input. Both default to 0, which adds no vertex."""
+    on the input. Both default to 0, which adds no vertex.
+
+    model.dis_spectral_norm wraps every D conv, d_dense_feat and d_out in
+    spectral normalization and OMITS the d_bn_* vertices: BatchNorm's
+    per-channel rescaling undoes the Lipschitz constraint, so SNGAN-style
+    discriminators run without it. Default off adds or changes no vertex."""
     m = cfg.model
     m.validate_regularisers()
     keep = 1.0 - m.dis_dropout
+    sn = bool(m.dis_spectral_norm)
     lr = cfg.optim.dis_learning_rate
     gb = GraphBuilder(seed=cfg.train.seed, optim_cfg=cfg.optim)
     gb.add_inputs("d_input")
@@ -82,8 +88,8 @@ def _dis_graph(cfg: GanConfig, stages: list[int], s_last: int) -> ComputationGra
     for i, c in enumerate(stages):
         name = f"d_conv_{i}"
         gb.add_layer(name, Conv2dLayer(c_prev, c, 4, 2, 1, activation="lrelu",
-                                       lr=lr), prev)
-        if i > 0:  # DCGAN: no BN on the first D layer
+                                       lr=lr, spectral_norm=sn), prev)
+        if i > 0 and not sn:  # DCGAN: no BN on the first D layer
             gb.add_layer(f"d_bn_{i}", BatchNormLayer(c, lr=lr), name)
             prev = f"d_bn_{i}"
         else:
@@ -93,14 +99,16 @@ def _dis_graph(cfg: GanConfig, stages: list[int], s_last: int) -> ComputationGra
             prev = f"d_drop_{i}"
         c_prev = c
     gb.add_layer("d_dense_feat", DenseLayer(c_prev * s_last * s_last, 1024,
-                                            activation="lrelu", lr=lr), prev,
+                                            activation="lrelu", lr=lr,
+                                            spectral_norm=sn), prev,
                  preprocessor=CnnToFeedForwardPreProcessor(channels_last=True))
     prev = "d_dense_feat"
     if m.dis_dropout > 0:
         gb.add_layer("d_drop_feat", DropoutLayer(keep), prev)
         prev = "d_drop_feat"
     gb.add_layer("d_out", OutputLayer(1024, 1, activation="sigmoid",
-                                      loss="xent", lr=lr), prev)
+                                      loss="xent", lr=lr, spectral_norm=sn),
+                 prev)
     gb.set_outputs("d_out")
     return gb.build().init()
 

@@ -43,23 +43,27 @@ def build_mlp_gan(cfg: GanConfig, hidden: int = 256
     # optional in-D regularisers (both default off: no extra vertex)
     cfg.model.validate_regularisers()
     drop, noise = cfg.model.dis_dropout, cfg.model.dis_input_noise_std
+    # spectral normalization on every D weight layer (D has no BatchNorm
+    # here, so the flag changes no vertex list)
+    sn = bool(cfg.model.dis_spectral_norm)
     prev = "d_input"
     if noise > 0:
         db.add_layer("d_noise_in", GaussianNoiseLayer(noise), prev)
         prev = "d_noise_in"
-    db.add_layer("d_dense_1", DenseLayer(f, hidden, "lrelu", dlr), prev)
+    db.add_layer("d_dense_1", DenseLayer(f, hidden, "lrelu", dlr,
+                                         spectral_norm=sn), prev)
     prev = "d_dense_1"
     if drop > 0:
         db.add_layer("d_drop_1", DropoutLayer(1.0 - drop), prev)
         prev = "d_drop_1"
-    db.add_layer("d_dense_feat", DenseLayer(hidden, hidden, "lrelu", dlr),
-                 prev)
+    db.add_layer("d_dense_feat", DenseLayer(hidden, hidden, "lrelu", dlr,
+                                            spectral_norm=sn), prev)
     prev = "d_dense_feat"
     if drop > 0:
         db.add_layer("d_drop_feat", DropoutLayer(1.0 - drop), prev)
         prev = "d_drop_feat"
-    db.add_layer("d_out", OutputLayer(hidden, 1, "sigmoid", "xent", dlr),
-                 prev)
+    db.add_layer("d_out", OutputLayer(hidden, 1, "sigmoid", "xent", dlr,
+                                      spectral_norm=sn), prev)
     db.set_outputs("d_out")
     dis = db.build().init()
     return gen, dis

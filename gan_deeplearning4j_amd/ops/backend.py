@@ -54,3 +54,51 @@ def has_hip_ext() -> bool:
         return True
     except RuntimeError:
         return False
+
+
+# ---------------------------------------------------------------- _spectral
+# The spectral-norm kernels live in a second module (ops/hip/spectral/) so
+# the frozen surface of _C stays what it is. Same contract: loud failure.
+_spectral = None
+_spectral_tried = False
+
+
+def _find_spectral_path() -> str | None:
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hits = glob.glob(os.path.join(here, "_spectral*.so"))
+    return hits[0] if hits else None
+
+
+def spectral_ext():
+    """Return the loaded spectral-norm extension module, raising if
+    unavailable."""
+    global _spectral, _spectral_tried
+    if _spectral is not None:
+        return _spectral
+    if not _spectral_tried:
+        _spectral_tried = True
+        path = _find_spectral_path()
+        if path is not None:
+            import importlib.util
+
+            spec = importlib.util.spec_from_file_location(
+                "gan_deeplearning4j_amd._spectral", path
+            )
+            mod = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(mod)  # type: ignore[union-attr]
+            _spectral = mod
+            return _spectral
+    raise RuntimeError(
+        "gan_deeplearning4j_amd spectral-norm extension (_spectral*.so) is "
+        "not built. Run `python setup.py build_ext --inplace` "
+        "(PYTORCH_ROCM_ARCH=gfx950). GPU ops refuse to run without their "
+        "native kernels."
+    )
+
+
+def has_spectral_ext() -> bool:
+    try:
+        spectral_ext()
+        return True
+    except RuntimeError:
+        return False

@@ -253,6 +253,53 @@ def gaussian_noise(x: torch.Tensor, state: torch.Tensor, stddev: float,
     return (x.float() + stddev * noise.float()).to(x.dtype)
 
 
+SPECTRAL_EPS = 1e-12
+
+
+def spectral_normalize(w: torch.Tensor, u: torch.Tensor, v: torch.Tensor,
+                       training: bool = True) -> torch.Tensor:
+    """Spectral normalization W / sigma with the semantics of
+    torch.nn.utils.spectral_norm (n_power_iterations=1, eps=1e-12, dim=0).
+
+    w is viewed as the matrix [w.shape[0], -1]; u [rows] and v [cols] are
+    the layer's persistent vectors. A training call does one power
+    iteration and overwrites u and v IN PLACE:
+
+        t = W^T u;  v = t / max(|t|, eps)
+        s = W v;    u = s / max(|s|, eps)
+        sigma = u . s;  W_sn = W / max(sigma, eps)
+
+    An eval call takes sigma = u . (W v) from the stored vectors and
+    writes nothing. The gradient treats u and v as constants, as torch
+    does: dW = (G - <G, W_sn> u v^T) / sigma, with the u, v and sigma of
+    the SAME forward (each call keeps its own copies, so a later forward
+    does not reach an earlier forward's backward).
+
+    One deliberate deviation from torch: the last division is guarded by
+    max(sigma, eps), so a zero matrix gives zeros, not NaN.
+
+    CPU: plain torch in any float dtype (computed in the wider of w's and
+    u's dtype). GPU: the _spectral HIP kernels (bf16 W, fp32 u/v)."""
+    if w.is_cuda:
+        from . import gpu_ops
+
+        return gpu_ops.spectral_normalize(w, u, v, training)
+    ct = torch.promote_types(w.dtype, u.dtype)
+    wm = w.reshape(w.shape[0], -1).to(ct)
+    if training:
+        with torch.no_grad():
+            wd = wm.detach()
+            v_c = F.normalize(torch.mv(wd.t(), u.to(ct)), dim=0,
+                              eps=SPECTRAL_EPS)
+            u_c = F.normalize(torch.mv(wd, v_c), dim=0, eps=SPECTRAL_EPS)
+            v.copy_(v_c)
+            u.copy_(u_c)
+    else:
+        u_c, v_c = u.detach().to(ct, copy=True), v.detach().to(ct, copy=True)
+    sigma = torch.dot(u_c, torch.mv(wm, v_c))
+    return (wm / sigma.clamp_min(SPECTRAL_EPS)).reshape(w.shape).to(w.dtype)
+
+
 def bce_with_logits_loss(
     logits: torch.Tensor, labels: torch.Tensor
 ) -> torch.Tensor:

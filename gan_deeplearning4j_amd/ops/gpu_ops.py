@@ -25,7 +25,7 @@ from typing import Optional
 
 import torch
 
-from .backend import hip_ext
+from .backend import hip_ext, spectral_ext
 
 ACT_CODES = {"identity": 0, None: 0, "tanh": 1, "sigmoid": 2, "lrelu": 3,
              "relu": 4}
@@ -1025,6 +1025,53 @@ def dropout(x, state, keep):
 
 def gaussian_noise(x, state, stddev):
     return _GaussianNoise.apply(x, state, stddev)
+
+
+# ============================================================ spectral norm
+class _SpectralNorm(torch.autograd.Function):
+    """W / sigma on the _spectral kernels (ops/hip/spectral/). Training
+    mode runs one power iteration and overwrites u, v on the device; the
+    kernels also hand back this call's OWN copies of u, v and sigma, which
+    is what backward uses: loss_d runs D twice before one backward, and
+    the second forward's state update must not reach the first's
+    gradient. Nothing crosses to the host, so a captured step replays."""
+
+    @staticmethod
+    def forward(ctx, w, u, v, training: bool):
+        ext = spectral_ext()
+        wb = _bf(w.detach())
+        if training:
+            w_sn, u_c, v_c, sig = ext.sn_forward(wb, u, v)[:4]
+        else:
+            w_sn, sig = ext.sn_forward_eval(wb, u, v)[:2]
+            u_c, v_c = u, v
+            if ctx.needs_input_grad[0]:
+                u_c, v_c = u.clone(), v.clone()
+        ctx.save_for_backward(w_sn, u_c, v_c, sig)
+        ctx.w_dtype = w.dtype
+        return w_sn
+
+    @staticmethod
+    def backward(ctx, g):
+        w_sn, u_c, v_c, sig = ctx.saved_tensors
+        dw = spectral_ext().sn_backward(_bf(g), w_sn, u_c, v_c, sig)[0]
+        return dw.to(ctx.w_dtype), None, None, None
+
+
+def spectral_normalize(w, u, v, training):
+    """GPU path of functional.spectral_normalize. Training: a fresh W_sn
+    per forward (its conv/linear packs are rebuilt per forward). Eval
+    without autograd: W_sn is cached on w like any other derived layout,
+    so serving keeps its packs across requests; a training forward drops
+    that entry because it moves u and v without touching w's version."""
+    if training:
+        cache = getattr(w, "_gdlj_cache", None)
+        if cache is not None:
+            cache[1].pop("sn_eval", None)
+    elif not (torch.is_grad_enabled() and w.requires_grad):
+        return _packed(w, "sn_eval", lambda: _SpectralNorm.apply(
+            w.detach(), u, v, False))
+    return _SpectralNorm.apply(w, u, v, training)
 
 
 # ==================================================================== losses

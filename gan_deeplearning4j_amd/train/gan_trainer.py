@@ -408,6 +408,13 @@ class GanTrainer:
                     p.copy_(p2)
                 for b, b2 in zip(live.buffers(), g2.buffers()):
                     b.copy_(b2)
+                # spectral-norm vectors travel in the zip; in place, so a
+                # captured step keeps reading the same storage
+                for name in live.layer_names():
+                    lyr, lyr2 = live.layers[name], g2.layers[name]
+                    if getattr(lyr, "spectral_norm", False):
+                        lyr.sn_u.copy_(lyr2.sn_u)
+                        lyr.sn_v.copy_(lyr2.sn_v)
             live.updater.load_state_dict(g2.updater.state_dict())
         state = torch.load(out / "trainer_state.pt", weights_only=True)
         self.it = int(state["it"])
