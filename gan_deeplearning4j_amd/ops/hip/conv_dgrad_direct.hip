@@ -28,22 +28,22 @@
 // Covers conv2/conv3-class dgrads of the DCGAN family; everything
 // else falls back to dcol+col2im (gemm.hip / im2col.hip).
 //
-// conv_dgrad_direct_p (below) is the persistent class-fused variant of
-// the same arithmetic; the launchers try it first and keep this kernel
-// as the fallback and A/B arm (GDLJ_DGRAD_PERSIST=0).
-// conv_dgrad_direct_w (further below) is its one-block-per-CU variant for
-// the 8x8 class grid, tried before it (GDLJ_DGRAD_WIDE=0 skips it).
+// Three kernels run this arithmetic: conv_dgrad_direct (one-shot: a block
+// per tile, class and c-tile), conv_dgrad_direct_p (persistent, class-fused,
+// two blocks per CU; the launchers try it before the one-shot kernel, which
+// stays as the fallback and A/B arm, GDLJ_DGRAD_PERSIST=0) and
+// conv_dgrad_direct_w (one block per CU, for the 8x8 class grid, tried
+// first; GDLJ_DGRAD_WIDE=0 skips it).  The arithmetic itself — geometry,
+// region stager, slice body, ctile, epilogue piece, partial reduction — is
+// in conv_dgrad_parts.h, once; the kernels below are the three pipelines
+// around it.
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 
 #include "common.h"
-
-namespace cdd {
-constexpr int BN = 64;
-constexpr int WSLICE_B = 16 * 1024;      // one [64c][128co] slice (2 subs)
-constexpr int WBUF_B = 2 * WSLICE_B;     // double buffer; >= ctile bytes
-}  // namespace cdd
+#include "conv_dgrad_parts.h"
 
 // 64-row x 64-k staged sub-tile, same swizzled layout/frag read as the
 // proven tn layout (conv_gather.h tn_stage_rows / gemm.hip tn_frag geometry).
@@ -63,16 +63,6 @@ DEV_INLINE void cdd_stage_w64(const unsigned short* __restrict__ g,
   }
 }
 
-DEV_INLINE bf16x8 cdd_wfrag(const char* lds, int row, int kslot) {
-  int byte = row * 128 + ((kslot ^ (row & 7)) * 16);
-  return *(const bf16x8*)(lds + byte);
-}
-
-// Blocks add their partials into row blockIdx.x & (kPartRows - 1) of the
-// bindings' [kPartRows][...] buffers (the one-shot grid can exceed kPartRows).
-static_assert((kPartRows & (kPartRows - 1)) == 0,
-              "kPartRows must be a power of two");
-
 // MI = pixel fragments per wave (BM = MI * 64).
 //
 // The same kernel serves the strided TRANSPOSED-conv forward (G side):
@@ -80,6 +70,9 @@ static_assert((kPartRows & (kPartRows - 1)) == 0,
 // W[ci,co,r,s] is the identical gather; pass x as `dy`, the
 // [R*S*Co8][Cin] "w2a" pack as `Wt`, bias_fwd + act for the fused
 // epilogue, and stats_part ([kPartRows][2*C8]) for fused BN statistics.
+//
+// The region is the window of the block's own class only; Ko8 need not be
+// a power of two here (stage_region<.., false>).
 template <int MI>
 __global__ __launch_bounds__(256, 2) void conv_dgrad_direct(
     const unsigned short* __restrict__ dy,   // [N][Ho][Wo][Ko8]
@@ -92,8 +85,7 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct(
     const unsigned short* __restrict__ zp,   // 16B zero page
     int Nb, int H, int W, int C8, int Ho, int Wo, int Ko8, long ldw,
     int R, int S, int pad, int act, float slope,
-    int Hc, int Wc, int rows_c, int rgn_rows, int rgn_cols,
-    FastDiv fWc) {
+    int Hc, int Wc, int rgn_rows, int rgn_cols, FastDiv fWc) {
   using namespace cdd;
   constexpr int BM = MI * 64;
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -110,63 +102,27 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct(
   const int cp0 = np0 - n * hwc;
   const int hc0 = cp0 / Wc;        // Wc | BM => whole class-row start
   const int cy = blockIdx.y;       // c-tile: channels [cy*64, cy*64+64)
-  const int qh = blockIdx.z >> 1;  // parity class
-  const int qw = blockIdx.z & 1;
+  const int cls = blockIdx.z;      // parity class
+  const int qh = cls >> 1, qw = cls & 1;
 
-  // class tap set: r = r0 + 2*rc (rc < Rc), s = s0 + 2*sc (sc < Sc)
-  const int r0 = (qh + pad) & 1;
-  const int s0 = (qw + pad) & 1;
-  const int Rc = (R - r0 + 1) >> 1;
-  const int Sc = (S - s0 + 1) >> 1;
-  const int rb0 = (qh + pad - r0) >> 1;   // dy row offset of tap rc=0
-  const int wb0 = (qw + pad - s0) >> 1;
-  const int lo_h = hc0 + rb0 - (Rc - 1);  // dy row of region row 0
-  const int lo_w = wb0 - (Sc - 1);        // dy col of region col 0
+  const int Rc = p_ntap(qh, pad, R), Sc = p_ntap(qw, pad, S);
+  const int rb0 = p_boff(qh, pad), wb0 = p_boff(qw, pad);
+  const int lo_h = p_lo(qh, pad, R);      // dy row of region row 0, - hc0
+  const int lo_w = p_lo(qw, pad, S);      // dy col of region col 0
 
-  // ---- stage the dy region: [rgn_rows][rgn_cols][Ko8], zero halo ----
-  // Source-side chunk swizzle (slot = j ^ (cc & mask)): without it the
-  // A-fragment reads of 16 consecutive-cc pixels land 256B apart =
-  // same LDS bank (16-way conflict); the xor spreads them 8-wide.
-  const int co_chunks = Ko8 >> 3;
-  const int cmask = co_chunks - 1;
-  const int ncell = rgn_rows * rgn_cols * co_chunks;
-  for (int cell = threadIdx.x; cell < ncell; cell += 256) {
-    int rc_ = cell / co_chunks;
-    int slot = cell - rc_ * co_chunks;
-    int rr = rc_ / rgn_cols;
-    int cc = rc_ - rr * rgn_cols;
-    int j = slot ^ (cc & cmask);
-    int hig = lo_h + rr;
-    int wig = lo_w + cc;
-    const unsigned short* src = zp;
-    if (hig >= 0 && hig < Ho && wig >= 0 && wig < Wo)
-      src = dy + (((long)n * Ho + hig) * Wo + wig) * Ko8 + j * 8;
-    char* dst = rgn + (cell & ~63) * 16;
-    GLDS16(src, dst);
-  }
+  stage_region<256, false>(dy, zp, rgn, n, 1, Nb, hc0 + lo_h, lo_w, rgn_rows,
+                           rgn_cols, Ho, Wo, Ko8);
 
   const int wid = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int fr = lane & 15, fq = lane >> 4;
-
-  // this lane's A-side class pixels: px_l = wid*(MI*16) + mi*16 + fr
-  int pxh[MI], pxw[MI];
-  #pragma unroll
-  for (int mi = 0; mi < MI; ++mi) {
-    int pxl = wid * (MI * 16) + mi * 16 + fr;
-    int hl = (int)fdiv((unsigned)pxl, fWc);
-    pxh[mi] = hl;                    // class-row within tile
-    pxw[mi] = pxl - hl * Wc;         // class-col (global: full width)
-  }
+  const int fr = threadIdx.x & 15;
+  const LanePx<MI> px = lane_px<MI>(wid * (MI * 16), 1, hwc, 0, fWc, Wc);
 
   const int nj = Ko8 >> 7;           // 128-co chunks per tap
   const int nslice = Rc * Sc * nj;
-  const unsigned short* wt_cy = Wt + (long)cy * 64 * ldw;
   auto wsrc_for = [&](int sl) {
     int tapj = sl / nj, j = sl - tapj * nj;
     int rc_ = tapj / Sc, sc_ = tapj - rc_ * Sc;
-    int tap = (r0 + 2 * rc_) * S + (s0 + 2 * sc_);
-    return wt_cy + (long)tap * C8 * ldw + j * 128;
+    return w_slice_src(Wt, ldw, C8, S, pad, cls, cy, rc_, sc_, j);
   };
 
   // first W slice, then one wait covers region + slice 0
@@ -176,10 +132,7 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct(
   __syncthreads();
 
   f32x4 acc[MI][4];
-  #pragma unroll
-  for (int i = 0; i < MI; ++i)
-    #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   for (int sl = 0; sl < nslice; ++sl) {
     int tapj = sl / nj;
@@ -195,43 +148,20 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct(
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
-    // region coordinates for this tap: rr = pxh + (Rc-1) - rc,
-    // cc = pxw + (Sc-1) - sc  (always in-grid; halo cells are zero)
-    long abase[MI];
-    int axor[MI];
-    #pragma unroll
-    for (int mi = 0; mi < MI; ++mi) {
-      int rr = pxh[mi] + (Rc - 1) - rc_;
-      int cc = pxw[mi] + (Sc - 1) - sc_;
-      abase[mi] = ((long)rr * rgn_cols + cc) * Ko8 * 2;
-      axor[mi] = cc & cmask;
-    }
-    const char* Wl = wbuf(cur);
-    #pragma unroll
-    for (int kc = 0; kc < 4; ++kc) {
-      int jc = j * 16 + kc * 4 + fq;       // 16B co-chunk within Ko8
-      bf16x8 a[MI], b[4];
-      #pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-        a[mi] = *(const bf16x8*)(rgn + abase[mi] +
-                                 ((jc ^ axor[mi]) << 4));
-      int sub = kc >> 1, kslot = (kc & 1) * 4 + fq;
-      #pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        b[ni] = cdd_wfrag(Wl + sub * 8 * 1024, ni * 16 + fr, kslot);
-      #pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-    }
+    slice_mfma<MI, 4, false>(acc, rgn, wbuf(cur), px, rb0 - rc_ - lo_h,
+                             wb0 - sc_ - lo_w, rgn_cols, Ko8, j, 0);
     __syncthreads();  // all waves done with wbuf(cur) before restage
   }
 
   // ---- epilogue: ctile in the W-buffer area; dgrad mode applies the
   // producer act' downstream, convT-fwd mode applies bias+act here ----
+  // This kernel keeps its own copy of the ctile transpose and the epilogue
+  // piece, the same expressions as write_ctile / epilogue_piece: through
+  // the shared ones (bias preloaded, pact / stats as arguments) it measured
+  // 0.05 ms (0.6 %) slower per call at the conv2 shapes, a block being only
+  // four to six slices long (profiles/dgrad_parts_refactor.md).
   unsigned short* ctile = (unsigned short*)wbuf(0);  // [BM][64]
+  const int fq = (threadIdx.x & 63) >> 4;
   #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
     #pragma unroll
@@ -250,9 +180,8 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct(
   __syncthreads();
   const int t2 = threadIdx.x;
   const int seg = t2 & 7;            // fixed c-block per thread
-  float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  float ssum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  float ssq[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  Partials<1> sums;
+  sums.clear();
   #pragma unroll
   for (int i = 0; i < BM / 32; ++i) {
     int piece = i * 256 + t2;        // BM*8 pieces = BM rows x 8 segs
@@ -270,56 +199,23 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct(
         float d = bf2f((unsigned short)v[jj]) *
                   act_bwd_from_y(bf2f((unsigned short)yv[jj]), act, slope);
         v[jj] = (short)f2bf(d);
-        bsum[jj] += d;
+        sums.bsum[0][jj] += d;
       }
     }
     if (stats_part != nullptr) {
       #pragma unroll
       for (int jj = 0; jj < 8; ++jj) {
         float yv = bf2f((unsigned short)v[jj]);
-        ssum[jj] += yv;
-        ssq[jj] += yv * yv;
+        sums.ssum[0][jj] += yv;
+        sums.ssq[0][jj] += yv * yv;
       }
     }
     *(s16x8*)(dx + addr) = v;
   }
-  // Block-level seg reductions in LDS before the global atomics: naive
-  // per-lane atomics (2048 lane-ops per block, 32-way duplicate
-  // addresses) serialized across ALL concurrent blocks and cost
-  // ~12 ms/call at the DCGAN-64 conv2 shape.  All conditions are
-  // block-uniform, so the inner barriers are safe.
-  float* red = (float*)rgn;  // region is dead after the MFMA loop
-  const int rrow = t2 >> 3;  // 32 contributor rows per seg
-  auto reduce_and_add = [&](const float* vec, float* dst) {
-    #pragma unroll
-    for (int jj = 0; jj < 8; ++jj)
-      red[(rrow * 8 + seg) * 8 + jj] = vec[jj];
-    __syncthreads();
-    for (int off = 16; off > 0; off >>= 1) {
-      if (rrow < off) {
-        #pragma unroll
-        for (int jj = 0; jj < 8; ++jj)
-          red[(rrow * 8 + seg) * 8 + jj] +=
-              red[((rrow + off) * 8 + seg) * 8 + jj];
-      }
-      __syncthreads();
-    }
-    if (rrow == 0) {
-      #pragma unroll
-      for (int jj = 0; jj < 8; ++jj)
-        atomicAdd(&dst[seg * 8 + jj], red[seg * 8 + jj]);
-    }
-    __syncthreads();  // red is reused by the next reduction
-  };
-  if (y0 != nullptr && part != nullptr)
-    reduce_and_add(
-        bsum, part + (long)(blockIdx.x & (kPartRows - 1)) * C8 + cy * 64);
-  if (stats_part != nullptr) {
-    float* srow =
-        stats_part + (long)(blockIdx.x & (kPartRows - 1)) * 2 * C8;
-    reduce_and_add(ssum, srow + cy * 64);
-    reduce_and_add(ssq, srow + C8 + cy * 64);
-  }
+  // all conditions are block-uniform, so the reductions' barriers are
+  // safe; the region is dead after the MFMA loop
+  flush_partials<32, 1>((float*)rgn, sums, y0 != nullptr ? part : nullptr,
+                        stats_part, C8, cy * 64);
 }
 
 // ---------------------------------------------------------------------
@@ -340,34 +236,13 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct(
 // double buffer never drains.  The next tile's region is issued right
 // after the tile's last MFMA slice, under the last epilogue.
 //
+// Barriers are cdd::p_lds_barrier (LDS traffic only): __syncthreads()
+// would drain the prefetched W slice / region at every barrier.
+//
 // Bias / BN-statistics partials stay in registers across all tiles and
-// go through the LDS tree + atomics once per block.  Per output element
-// the accumulation sequence (taps, 128-co chunk, kc) and the epilogue
-// expressions are those of conv_dgrad_direct, so dx / y are
-// bit-identical; only the order of the fp32 partial sums differs.
-namespace cdd {
-// per-axis parity-class geometry: first tap, tap count, dy offset of
-// tap 0 (class pixel h reads dy rows h + boff - k, k < ntap)
-DEV_INLINE int p_tap0(int q, int pad) { return (q + pad) & 1; }
-DEV_INLINE int p_ntap(int q, int pad, int R) {
-  return (R - p_tap0(q, pad) + 1) >> 1;
-}
-DEV_INLINE int p_boff(int q, int pad) {
-  return (q + pad - p_tap0(q, pad)) >> 1;
-}
-// Workgroup barrier for LDS traffic only.  __syncthreads() carries a
-// release fence that drains vmcnt to 0, i.e. waits for the prefetched
-// W slice / region at every barrier and serializes the pipeline
-// (same finding as gemm8p.hip).  This one completes the wave's own LDS
-// reads/writes and leaves the LDS-DMA loads in flight; their arrival
-// is guarded by the counted vmcnt waits.
-DEV_INLINE void p_lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-}  // namespace cdd
-
+// go through the LDS tree + atomics once per block; only the order of
+// those fp32 partial sums differs from the one-shot kernel.
+//
 // PACT = y0 given (producer act-backward epilogue).
 template <int MI, int NCT, bool PACT>
 __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
@@ -391,79 +266,43 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
   auto wbuf = [&](int i) -> char* { return lds + rgn_b + i * WSLICE_B; };
 
   const int rows_c = BM / Wc;
-  const int tpi = (Hc * Wc) / BM;          // pixel tiles per image
-  const int co_chunks = Ko8 >> 3;          // power of two (launcher)
-  const int cmask = co_chunks - 1;
-  const int csh = 31 - __builtin_clz(co_chunks);
-  const int ncell = rgn_rows * rgn_cols * co_chunks;
+  const int hwc = Hc * Wc;
+  const int tpi = hwc / BM;                // pixel tiles per image
   const int nj = Ko8 >> 7;                 // 128-co chunks per tap
 
   // union column window over both column parities
-  const int lo_w = min(p_boff(0, pad) - (p_ntap(0, pad, S) - 1),
-                       p_boff(1, pad) - (p_ntap(1, pad, S) - 1));
+  const int lo_w = p_union_lo(pad, S);
   // union row window: both row parities, or the tile's own one (qsplit)
   auto row_lo = [&](int tile) {
-    int a = p_boff(0, pad) - (p_ntap(0, pad, R) - 1);
-    int b = p_boff(1, pad) - (p_ntap(1, pad, R) - 1);
-    return qsplit ? ((tile & 1) ? b : a) : min(a, b);
+    return qsplit ? p_lo(tile & 1, pad, R) : p_union_lo(pad, R);
   };
 
-  // ---- stage a tile's region: [rgn_rows][rgn_cols][Ko8], zero halo,
-  // source-side chunk swizzle slot = j ^ (cc & cmask) as above ----
-  auto stage_region = [&](int tile) {
+  // a tile's region; Ko8 is a power of two (launcher); every tile lies
+  // inside the batch
+  auto stage_tile = [&](int tile) {
     int pt = qsplit ? (tile >> 1) : tile;
     int n = pt / tpi;
     int hc0 = (pt - n * tpi) * rows_c;
-    int h0 = hc0 + row_lo(tile);
-    for (int cell = threadIdx.x; cell < ncell; cell += 256) {
-      int rc_ = cell >> csh;
-      int slot = cell & cmask;
-      int rr = rc_ / rgn_cols;
-      int cc = rc_ - rr * rgn_cols;
-      int j = slot ^ (cc & cmask);
-      int hig = h0 + rr;
-      int wig = lo_w + cc;
-      const unsigned short* src = zp;
-      if (hig >= 0 && hig < Ho && wig >= 0 && wig < Wo)
-        src = dy + (((long)n * Ho + hig) * Wo + wig) * Ko8 + j * 8;
-      char* dst = rgn + (cell & ~63) * 16;
-      GLDS16(src, dst);
-    }
+    stage_region<256, true>(dy, zp, rgn, n, 1, n + 1, hc0 + row_lo(tile),
+                            lo_w, rgn_rows, rgn_cols, Ho, Wo, Ko8);
   };
 
   // W source of slice sl of (class cls, c-tile ct)
   auto wsrc_for = [&](int cls, int ct, int sl) {
-    int qh = cls >> 1, qw = cls & 1;
-    int r0 = p_tap0(qh, pad), s0 = p_tap0(qw, pad);
-    int Sc = p_ntap(qw, pad, S);
+    int Sc = p_ntap(cls & 1, pad, S);
     int tapj = sl / nj, j = sl - tapj * nj;
     int rc_ = tapj / Sc, sc_ = tapj - rc_ * Sc;
-    int tap = (r0 + 2 * rc_) * S + (s0 + 2 * sc_);
-    return Wt + ((long)tap * C8 + ct * 64) * ldw + j * 128;
+    return w_slice_src(Wt, ldw, C8, S, pad, cls, ct, rc_, sc_, j);
   };
 
   const int wid = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int fr = lane & 15, fq = lane >> 4;
-
-  // this lane's A-side class pixels: px_l = wid*(MI*16) + mi*16 + fr
-  int pxh[MI], pxw[MI];
-  #pragma unroll
-  for (int mi = 0; mi < MI; ++mi) {
-    int pxl = wid * (MI * 16) + mi * 16 + fr;
-    int hl = (int)fdiv((unsigned)pxl, fWc);
-    pxh[mi] = hl;
-    pxw[mi] = pxl - hl * Wc;
-  }
+  const int fr = threadIdx.x & 15;
+  const LanePx<MI> px = lane_px<MI>(wid * (MI * 16), 1, hwc, 0, fWc, Wc);
 
   const int t2 = threadIdx.x;
   const int seg = t2 & 7;            // fixed c-block per thread
-  float bsum[NCT][8], ssum[NCT][8], ssq[NCT][8];
-  #pragma unroll
-  for (int k = 0; k < NCT; ++k)
-    #pragma unroll
-    for (int jj = 0; jj < 8; ++jj)
-      bsum[k][jj] = ssum[k][jj] = ssq[k][jj] = 0.f;
+  Partials<NCT> sums;
+  sums.clear();
 
   // convT-forward bias of this lane's columns, loaded once: a global
   // load inside the epilogue would make the compiler drain the
@@ -484,7 +323,7 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
   // covers both (loads complete in issue order)
   int tile = blockIdx.x;
   const int cls0 = qsplit ? (tile & 1) * 2 : 0;
-  stage_region(tile);
+  stage_tile(tile);
   cdd_stage_w64(wsrc_for(cls0, 0, 0), ldw, 0, wbuf(0));
   cdd_stage_w64(wsrc_for(cls0, 0, 0), ldw, 64, wbuf(0) + 8 * 1024);
 
@@ -508,10 +347,7 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
       for (int ct = 0; ct < NCT; ++ct) {
         const bool last_ct = (cls + 1 == ce) && (ct + 1 == NCT);
         f32x4 acc[MI][4];
-        #pragma unroll
-        for (int i = 0; i < MI; ++i)
-          #pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
 
         for (int sl = 0; sl < nslice; ++sl, ++g) {
           int tapj = sl / nj;
@@ -542,43 +378,14 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           }
           p_lds_barrier();
-          // region coordinates for this tap (always in-grid; halo
-          // cells are zero)
-          long abase[MI];
-          int axor[MI];
-          #pragma unroll
-          for (int mi = 0; mi < MI; ++mi) {
-            int rr = pxh[mi] + rb0 - rc_ - lo_h;
-            int cc = pxw[mi] + wb0 - sc_ - lo_w;
-            abase[mi] = ((long)rr * rgn_cols + cc) * Ko8 * 2;
-            axor[mi] = cc & cmask;
-          }
-          const char* Wl = wbuf(cur);
-          #pragma unroll
-          for (int kc = 0; kc < 4; ++kc) {
-            int jc = j * 16 + kc * 4 + fq;   // 16B co-chunk within Ko8
-            bf16x8 a[MI], b[4];
-            #pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-              a[mi] = *(const bf16x8*)(rgn + abase[mi] +
-                                       ((jc ^ axor[mi]) << 4));
-            int sub = kc >> 1, kslot = (kc & 1) * 4 + fq;
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-              b[ni] = cdd_wfrag(Wl + sub * 8 * 1024, ni * 16 + fr, kslot);
-            #pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-              #pragma unroll
-              for (int ni = 0; ni < 4; ++ni)
-                acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    a[mi], b[ni], acc[mi][ni], 0, 0, 0);
-          }
+          slice_mfma<MI, 4, false>(acc, rgn, wbuf(cur), px, rb0 - rc_ - lo_h,
+                                   wb0 - sc_ - lo_w, rgn_cols, Ko8, j, 0);
           p_lds_barrier();  // all waves done with wbuf(cur) + region
         }
 
         // the tile's last MFMA slice is done: the region is dead, put
         // the next tile's region in flight under this epilogue
-        if (last_ct && has_next) stage_region(ntile);
+        if (last_ct && has_next) stage_tile(ntile);
         // keep the region loads ahead of the epilogue's stores (the
         // counted wait above relies on that order)
         asm volatile("" ::: "memory");
@@ -591,11 +398,11 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
         #pragma unroll
         for (int i = 0; i < BM / 32; ++i) {
           int row = (i * 256 + t2) >> 3;  // BM*8 pieces = BM rows x 8 segs
-          int hl = (int)fdiv((unsigned)row, fWc);
-          int wcl = row - hl * Wc;
-          int hi = qh + 2 * (hc0 + hl);
-          int wi = qw + 2 * wcl;
+          ClassPx p = class_px(row, 1, hwc, fWc, Wc);
+          int hi = qh + 2 * (hc0 + p.h);
+          int wi = qw + 2 * p.w;
           eaddr[i] = (((long)n * H + hi) * W + wi) * C8 + ct * 64 + seg * 8;
+          yin[i] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
         }
         if constexpr (PACT) {
           #pragma unroll
@@ -606,24 +413,16 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
         // ---- epilogue: ctile = the W buffer the last slice released
         // (the in-flight prefetch targets the other one) ----
         unsigned short* ctile = (unsigned short*)wbuf((g - 1) & 1);
+        float bv[4];
         #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
+        for (int ni = 0; ni < 4; ++ni) {
+          bv[ni] = 0.f;
           #pragma unroll
-          for (int ni = 0; ni < 4; ++ni) {
-            int lc = ni * 16 + fr;
-            float bv = 0.f;
-            #pragma unroll
-            for (int k = 0; k < NCT; ++k)
-              if (ct == k) bv = biasv[k][ni];
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              int lr = wid * (MI * 16) + mi * 16 + fq * 4 + r;
-              float v = acc[mi][ni][r];
-              if (bias_fwd != nullptr) v = act_fwd(v + bv, act, slope);
-              ctile[lr * 64 + lc] = f2bf(v);
-            }
-          }
+          for (int k = 0; k < NCT; ++k)
+            if (ct == k) bv[ni] = biasv[k][ni];
         }
+        write_ctile<MI, 4>(ctile, acc, bv, bias_fwd != nullptr, act, slope,
+                           wid * (MI * 16), 0);
         p_lds_barrier();
         if constexpr (PACT) {
           // take the wait for all fetched y0 pieces here, once; left to
@@ -635,34 +434,9 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
         #pragma unroll
         for (int i = 0; i < BM / 32; ++i) {
           int row = (i * 256 + t2) >> 3;
-          const long addr = eaddr[i];
-          s16x8 v = *(const s16x8*)(ctile + row * 64 + seg * 8);
-          if constexpr (PACT) {
-            const s16x8 yv = yin[i];
-            #pragma unroll
-            for (int jj = 0; jj < 8; ++jj) {
-              float d = bf2f((unsigned short)v[jj]) *
-                        act_bwd_from_y(bf2f((unsigned short)yv[jj]), act,
-                                       slope);
-              v[jj] = (short)f2bf(d);
-              #pragma unroll
-              for (int k = 0; k < NCT; ++k)
-                if (ct == k) bsum[k][jj] += d;
-            }
-          }
-          if (stats_part != nullptr) {
-            #pragma unroll
-            for (int jj = 0; jj < 8; ++jj) {
-              float yv = bf2f((unsigned short)v[jj]);
-              #pragma unroll
-              for (int k = 0; k < NCT; ++k)
-                if (ct == k) {
-                  ssum[k][jj] += yv;
-                  ssq[k][jj] += yv * yv;
-                }
-            }
-          }
-          *(s16x8*)(dx + addr) = v;
+          epilogue_piece<NCT>(ctile + row * 64 + seg * 8, dx + eaddr[i], PACT,
+                              yin[i], stats_part != nullptr, ct, act, slope,
+                              sums);
         }
         p_lds_barrier();  // ctile reads done before it is restaged as W
       }
@@ -671,41 +445,8 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
 
   // ---- once per block: LDS tree + atomics over the register partials
   // (region and W buffers are dead, nothing is in flight) ----
-  float* red = (float*)rgn;
-  const int rrow = t2 >> 3;  // 32 contributor rows per seg
-  auto reduce_and_add = [&](const float* vec, float* dst) {
-    #pragma unroll
-    for (int jj = 0; jj < 8; ++jj)
-      red[(rrow * 8 + seg) * 8 + jj] = vec[jj];
-    __syncthreads();
-    for (int off = 16; off > 0; off >>= 1) {
-      if (rrow < off) {
-        #pragma unroll
-        for (int jj = 0; jj < 8; ++jj)
-          red[(rrow * 8 + seg) * 8 + jj] +=
-              red[((rrow + off) * 8 + seg) * 8 + jj];
-      }
-      __syncthreads();
-    }
-    if (rrow == 0) {
-      #pragma unroll
-      for (int jj = 0; jj < 8; ++jj)
-        atomicAdd(&dst[seg * 8 + jj], red[seg * 8 + jj]);
-    }
-    __syncthreads();  // red is reused by the next reduction
-  };
-  #pragma unroll
-  for (int k = 0; k < NCT; ++k) {
-    if (PACT && part != nullptr)
-      reduce_and_add(
-          bsum[k], part + (long)(blockIdx.x & (kPartRows - 1)) * C8 + k * 64);
-    if (stats_part != nullptr) {
-      float* srow =
-          stats_part + (long)(blockIdx.x & (kPartRows - 1)) * 2 * C8;
-      reduce_and_add(ssum[k], srow + k * 64);
-      reduce_and_add(ssq[k], srow + C8 + k * 64);
-    }
-  }
+  flush_partials<32, NCT>((float*)rgn, sums, PACT ? part : nullptr,
+                          stats_part, C8, 0);
 }
 
 // ---------------------------------------------------------------------
@@ -730,8 +471,8 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
 // A slice costs ONE barrier: wait for slice g, barrier, issue slice g+2
 // into the buffer of slice g-1 (every wave has read it: its LDS reads
 // are complete when it arrives at the barrier), fetch all fragments of
-// slice g, then its MFMAs, which run into the next slice's scalar work
-// and wait.
+// slice g, then its MFMAs (slice_mfma's FETCH_AHEAD), which run into the
+// next slice's scalar work and wait.
 //
 // Wait accounting (loads and stores retire in issue order).  Per thread
 // a slice is 2 loads, an epilogue ST = BM/64 dx stores, and with PACT
@@ -754,10 +495,8 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_direct_p(
 //
 // Wave tile: 32 px x 32 c (4 pixel groups x 2 channel halves), 4 MFMA
 // per kc against 4 ds_read_b128 (conv_dgrad_direct_p<1,..>: 4 against
-// 5).  Per output element the accumulation sequence
-// (tap, 128-co chunk, kc, one MFMA chain) and the epilogue expressions
-// are those of conv_dgrad_direct_p: dx / y are bit-identical to it; the
-// fp32 bias / BN partials are summed in another order.
+// 5).  The fp32 bias / BN partials are summed in another order than in
+// the other two kernels.
 namespace cdd {
 constexpr int W_NBUF = 3;
 constexpr int W_THREADS = 512;
@@ -809,44 +548,20 @@ __global__ __launch_bounds__(512, 1) void conv_dgrad_direct_w(
 
   const int hwc = Hc * Wc;            // class pixels per image
   const int imgs = BM / hwc;          // 2 (launcher)
-  const int cpi = rgn_rows * rgn_cols;          // region cells per image
-  const int rgn_img_b = cpi * Ko8 * 2;
+  const int rgn_img_b = rgn_rows * rgn_cols * Ko8 * 2;
   const int rgn_b = imgs * rgn_img_b;
   auto wbuf = [&](int i) -> char* { return lds + rgn_b + i * WSLICE_B; };
-
-  const int co_chunks = Ko8 >> 3;     // power of two (launcher)
-  const int cmask = co_chunks - 1;
-  const int csh = 31 - __builtin_clz(co_chunks);
-  const int ncell = imgs * cpi * co_chunks;
   const int nj = Ko8 >> 7;            // 128-co chunks per tap
 
   // union window over both parities, per axis
-  const int lo_w = min(p_boff(0, pad) - (p_ntap(0, pad, S) - 1),
-                       p_boff(1, pad) - (p_ntap(1, pad, S) - 1));
-  const int lo_h = min(p_boff(0, pad) - (p_ntap(0, pad, R) - 1),
-                       p_boff(1, pad) - (p_ntap(1, pad, R) - 1));
+  const int lo_w = p_union_lo(pad, S);
+  const int lo_h = p_union_lo(pad, R);
 
-  // ---- stage a tile's regions: [imgs][rgn_rows][rgn_cols][Ko8], zero
-  // halo, an image past Nb all zero; source-side chunk swizzle ----
-  auto stage_region = [&](int tile) {
-    const int n0 = tile * imgs;
-    for (int cell = threadIdx.x; cell < ncell; cell += W_THREADS) {
-      int rc_ = cell >> csh;
-      int slot = cell & cmask;
-      int img = rc_ >= cpi ? 1 : 0;
-      int rci = rc_ - img * cpi;
-      int rr = rci / rgn_cols;
-      int cc = rci - rr * rgn_cols;
-      int j = slot ^ (cc & cmask);
-      int hig = lo_h + rr;
-      int wig = lo_w + cc;
-      int n = n0 + img;
-      const unsigned short* src = zp;
-      if (n < Nb && hig >= 0 && hig < Ho && wig >= 0 && wig < Wo)
-        src = dy + (((long)n * Ho + hig) * Wo + wig) * Ko8 + j * 8;
-      char* dst = rgn + (cell & ~63) * 16;
-      GLDS16(src, dst);
-    }
+  // a tile's regions, an image past Nb all zero; Ko8 is a power of two
+  // (launcher)
+  auto stage_tile = [&](int tile) {
+    stage_region<W_THREADS, true>(dy, zp, rgn, tile * imgs, imgs, Nb, lo_h,
+                                  lo_w, rgn_rows, rgn_cols, Ho, Wo, Ko8);
   };
 
   // issue cursor of the endless W stream, in the consumer's order:
@@ -854,16 +569,14 @@ __global__ __launch_bounds__(512, 1) void conv_dgrad_direct_w(
   // divisions: the slice loop's scalar work is on the critical path)
   int i_cls = 0, i_ct = 0, i_rc = 0, i_sc = 0, i_j = 0;
   auto issue_w = [&](int buf) {
-    const int qh = i_cls >> 1, qw = i_cls & 1;
-    const int tap = (p_tap0(qh, pad) + 2 * i_rc) * S + p_tap0(qw, pad) +
-                    2 * i_sc;
-    w_stage_slice(Wt + ((long)tap * C8 + i_ct * 64) * ldw + i_j * 128, ldw,
-                  wbuf(buf));
+    w_stage_slice(
+        w_slice_src(Wt, ldw, C8, S, pad, i_cls, i_ct, i_rc, i_sc, i_j), ldw,
+        wbuf(buf));
     if (++i_j == nj) {
       i_j = 0;
-      if (++i_sc == p_ntap(qw, pad, S)) {
+      if (++i_sc == p_ntap(i_cls & 1, pad, S)) {
         i_sc = 0;
-        if (++i_rc == p_ntap(qh, pad, R)) {
+        if (++i_rc == p_ntap(i_cls >> 1, pad, R)) {
           i_rc = 0;
           if (++i_ct == NCT) {
             i_ct = 0;
@@ -875,34 +588,20 @@ __global__ __launch_bounds__(512, 1) void conv_dgrad_direct_w(
   };
 
   const int wid = threadIdx.x >> 6;
-  const int lane = threadIdx.x & 63;
-  const int fr = lane & 15, fq = lane >> 4;
+  const int fr = threadIdx.x & 15;
   const int pg = wid / WC;            // pixel group of this wave
   const int ch = wid - pg * WC;       // channel part of this wave
   const int wrow0 = pg * (MI * 16);   // first tile row of this wave
+  const int wcol0 = ch * (NI * 16);   // first channel of this wave
 
-  // this lane's A-side class pixels (a 16-pixel fragment never
-  // straddles two images: hwc is a multiple of 16)
-  int pxa[MI], pxh[MI], pxw[MI];
-  #pragma unroll
-  for (int mi = 0; mi < MI; ++mi) {
-    int pxl = wrow0 + mi * 16 + fr;
-    int img = pxl >= hwc ? 1 : 0;
-    int rem = pxl - img * hwc;
-    int hl = (int)fdiv((unsigned)rem, fWc);
-    pxa[mi] = img * rgn_img_b;
-    pxh[mi] = hl;
-    pxw[mi] = rem - hl * Wc;
-  }
+  // a 16-pixel fragment never straddles two images: hwc is a multiple
+  // of 16
+  const LanePx<MI> px = lane_px<MI>(wrow0, imgs, hwc, rgn_img_b, fWc, Wc);
 
   const int t2 = threadIdx.x;
   const int seg = t2 & 7;             // fixed c-block per thread
-  float bsum[NCT][8], ssum[NCT][8], ssq[NCT][8];
-  #pragma unroll
-  for (int k = 0; k < NCT; ++k)
-    #pragma unroll
-    for (int jj = 0; jj < 8; ++jj)
-      bsum[k][jj] = ssum[k][jj] = ssq[k][jj] = 0.f;
+  Partials<NCT> sums;
+  sums.clear();
 
   // convT-forward bias of this lane's columns, loaded and consumed ahead
   // of every LDS-DMA load (see conv_dgrad_direct_p)
@@ -912,7 +611,7 @@ __global__ __launch_bounds__(512, 1) void conv_dgrad_direct_w(
     #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
       biasv[k][ni] = bias_fwd != nullptr
-                         ? bias_fwd[k * 64 + ch * (NI * 16) + ni * 16 + fr]
+                         ? bias_fwd[k * 64 + wcol0 + ni * 16 + fr]
                          : 0.f;
       asm volatile("" : "+v"(biasv[k][ni]));
     }
@@ -923,18 +622,16 @@ __global__ __launch_bounds__(512, 1) void conv_dgrad_direct_w(
   #pragma unroll
   for (int e = 0; e < ST; ++e) {
     int row = (e * W_THREADS + t2) >> 3;
-    int img = row >= hwc ? 1 : 0;
-    int rem = row - img * hwc;
-    int hl = (int)fdiv((unsigned)rem, fWc);
+    ClassPx p = class_px(row, imgs, hwc, fWc, Wc);
     erow[e] = row;
-    eimg[e] = img;
-    eoff[e] = (2 * hl * W + 2 * (rem - hl * Wc)) * C8 + seg * 8;
+    eimg[e] = p.img;
+    eoff[e] = (2 * p.h * W + 2 * p.w) * C8 + seg * 8;
   }
 
   // prologue: first region + the first two W slices; the first in-loop
   // wait covers the region and slice 0
   int tile = blockIdx.x;
-  stage_region(tile);
+  stage_tile(tile);
   issue_w(0);
   issue_w(1);
 
@@ -967,20 +664,16 @@ __global__ __launch_bounds__(512, 1) void conv_dgrad_direct_w(
           evalid[e] = n < Nb;
           eaddr[e] = ((long)n * H + qh) * W * C8 + (long)qw * C8 + eoff[e] +
                      ct * 64;
+          yin[e] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
         }
         if constexpr (PACT) {
           #pragma unroll
-          for (int e = 0; e < ST; ++e) {
-            yin[e] = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
+          for (int e = 0; e < ST; ++e)
             if (evalid[e]) yin[e] = *(const s16x8*)(y0 + eaddr[e]);
-          }
         }
 
         f32x4 acc[MI][NI];
-        #pragma unroll
-        for (int i = 0; i < MI; ++i)
-          #pragma unroll
-          for (int j = 0; j < NI; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
 
         bool first_of_ct = true;
         for (int rc_ = 0; rc_ < Rc; ++rc_)
@@ -1006,45 +699,8 @@ __global__ __launch_bounds__(512, 1) void conv_dgrad_direct_w(
           // slice, whose buffer takes the slice two ahead
           p_lds_barrier();
           issue_w(cur == 0 ? 2 : cur - 1);
-          // region coordinates for this tap (always in-grid; halo
-          // cells are zero)
-          int abase[MI];
-          int axor[MI];
-          #pragma unroll
-          for (int mi = 0; mi < MI; ++mi) {
-            int rr = pxh[mi] + rb0 - rc_ - lo_h;
-            int cc = pxw[mi] + wb0 - sc_ - lo_w;
-            abase[mi] = pxa[mi] + (rr * rgn_cols + cc) * Ko8 * 2;
-            axor[mi] = cc & cmask;
-          }
-          const char* Wl = wbuf(cur);
-          // all fragments of the slice are fetched ahead of its MFMAs:
-          // fetched per kc, every kc step exposes an LDS round trip that
-          // two waves per SIMD cannot cover
-          bf16x8 a[4][MI], b[4][NI];
-          #pragma unroll
-          for (int kc = 0; kc < 4; ++kc) {
-            int jc = j * 16 + kc * 4 + fq;   // 16B co-chunk within Ko8
-            #pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-              a[kc][mi] = *(const bf16x8*)(rgn + abase[mi] +
-                                           ((jc ^ axor[mi]) << 4));
-            int sub = kc >> 1, kslot = (kc & 1) * 4 + fq;
-            #pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-              b[kc][ni] = cdd_wfrag(Wl + sub * 8 * 1024,
-                                    ch * (NI * 16) + ni * 16 + fr, kslot);
-          }
-          // keep the scheduler from sinking the reads back to their uses
-          __builtin_amdgcn_sched_barrier(0);
-          #pragma unroll
-          for (int kc = 0; kc < 4; ++kc)
-            #pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-              #pragma unroll
-              for (int ni = 0; ni < NI; ++ni)
-                acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                    a[kc][mi], b[kc][ni], acc[mi][ni], 0, 0, 0);
+          slice_mfma<MI, NI, true>(acc, rgn, wbuf(cur), px, rb0 - rc_ - lo_h,
+                                   wb0 - sc_ - lo_w, rgn_cols, Ko8, j, wcol0);
           cur = cur == 2 ? 0 : cur + 1;
         }
         // every wave is done with the last slice's W buffer (the ctile)
@@ -1055,7 +711,7 @@ __global__ __launch_bounds__(512, 1) void conv_dgrad_direct_w(
         // this epilogue; with PACT after the y0 pieces are taken (below),
         // so that their wait does not cover it
         if constexpr (!PACT) {
-          if (last_ct && has_next) stage_region(ntile);
+          if (last_ct && has_next) stage_tile(ntile);
         }
         asm volatile("" ::: "memory");
 
@@ -1063,24 +719,16 @@ __global__ __launch_bounds__(512, 1) void conv_dgrad_direct_w(
         // (slices g+1, g+2 sit in the other two) ----
         unsigned short* ctile =
             (unsigned short*)wbuf(cur == 0 ? 2 : cur - 1);
+        float bv[NI];
         #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
+        for (int ni = 0; ni < NI; ++ni) {
+          bv[ni] = 0.f;
           #pragma unroll
-          for (int ni = 0; ni < NI; ++ni) {
-            int lc = ch * (NI * 16) + ni * 16 + fr;
-            float bv = 0.f;
-            #pragma unroll
-            for (int k = 0; k < NCT; ++k)
-              if (ct == k) bv = biasv[k][ni];
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              int lr = wrow0 + mi * 16 + fq * 4 + r;
-              float v = acc[mi][ni][r];
-              if (bias_fwd != nullptr) v = act_fwd(v + bv, act, slope);
-              ctile[lr * 64 + lc] = f2bf(v);
-            }
-          }
+          for (int k = 0; k < NCT; ++k)
+            if (ct == k) bv[ni] = biasv[k][ni];
         }
+        write_ctile<MI, NI>(ctile, acc, bv, bias_fwd != nullptr, act, slope,
+                            wrow0, wcol0);
         p_lds_barrier();
         if constexpr (PACT) {
           // Take the wait for the y0 pieces here, once.  The compiler
@@ -1091,40 +739,15 @@ __global__ __launch_bounds__(512, 1) void conv_dgrad_direct_w(
           // that wait.
           #pragma unroll
           for (int e = 0; e < ST; ++e) asm volatile("" : "+v"(yin[e]));
-          if (last_ct && has_next) stage_region(ntile);
+          if (last_ct && has_next) stage_tile(ntile);
           asm volatile("" ::: "memory");
         }
         #pragma unroll
         for (int e = 0; e < ST; ++e) {
           if (!evalid[e]) continue;
-          const long addr = eaddr[e];
-          s16x8 v = *(const s16x8*)(ctile + erow[e] * 64 + seg * 8);
-          if constexpr (PACT) {
-            const s16x8 yv = yin[e];
-            #pragma unroll
-            for (int jj = 0; jj < 8; ++jj) {
-              float d = bf2f((unsigned short)v[jj]) *
-                        act_bwd_from_y(bf2f((unsigned short)yv[jj]), act,
-                                       slope);
-              v[jj] = (short)f2bf(d);
-              #pragma unroll
-              for (int k = 0; k < NCT; ++k)
-                if (ct == k) bsum[k][jj] += d;
-            }
-          }
-          if (stats_part != nullptr) {
-            #pragma unroll
-            for (int jj = 0; jj < 8; ++jj) {
-              float yv = bf2f((unsigned short)v[jj]);
-              #pragma unroll
-              for (int k = 0; k < NCT; ++k)
-                if (ct == k) {
-                  ssum[k][jj] += yv;
-                  ssq[k][jj] += yv * yv;
-                }
-            }
-          }
-          *(s16x8*)(dx + addr) = v;
+          epilogue_piece<NCT>(ctile + erow[e] * 64 + seg * 8, dx + eaddr[e],
+                              PACT, yin[e], stats_part != nullptr, ct, act,
+                              slope, sums);
         }
         // the ctile reads are complete before the next slice's barrier,
         // behind which the buffer is restaged
@@ -1136,164 +759,154 @@ __global__ __launch_bounds__(512, 1) void conv_dgrad_direct_w(
   // tile, then LDS tree + atomics over the register partials ----
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  float* red = (float*)rgn;
-  const int rrow = t2 >> 3;  // 64 contributor rows per seg
-  auto reduce_and_add = [&](const float* vec, float* dst) {
-    #pragma unroll
-    for (int jj = 0; jj < 8; ++jj)
-      red[(rrow * 8 + seg) * 8 + jj] = vec[jj];
-    __syncthreads();
-    for (int off = 32; off > 0; off >>= 1) {
-      if (rrow < off) {
-        #pragma unroll
-        for (int jj = 0; jj < 8; ++jj)
-          red[(rrow * 8 + seg) * 8 + jj] +=
-              red[((rrow + off) * 8 + seg) * 8 + jj];
-      }
-      __syncthreads();
-    }
-    if (rrow == 0) {
-      #pragma unroll
-      for (int jj = 0; jj < 8; ++jj)
-        atomicAdd(&dst[seg * 8 + jj], red[seg * 8 + jj]);
-    }
-    __syncthreads();  // red is reused by the next reduction
-  };
-  #pragma unroll
-  for (int k = 0; k < NCT; ++k) {
-    if (PACT && part != nullptr)
-      reduce_and_add(
-          bsum[k], part + (long)(blockIdx.x & (kPartRows - 1)) * C8 + k * 64);
-    if (stats_part != nullptr) {
-      float* srow =
-          stats_part + (long)(blockIdx.x & (kPartRows - 1)) * 2 * C8;
-      reduce_and_add(ssum[k], srow + k * 64);
-      reduce_and_add(ssq[k], srow + C8 + k * 64);
-    }
-  }
+  flush_partials<W_THREADS / 8, NCT>((float*)rgn, sums,
+                                     PACT ? part : nullptr, stats_part, C8,
+                                     0);
 }
 
-// one-time dynamic-LDS opt-in for every instantiation of the kernels
-static void cdd_set_attrs_once() {
+// ---------------------------------------------------------------------
+// Every instantiation that exists, once: O(MI) one-shot, P(MI, NCT, PACT)
+// persistent, W(NCT, PACT) wide.  The dynamic-LDS opt-in and the three
+// dispatches below are generated from it, so an instantiation cannot be
+// launched without its opt-in.
+#define CDD_INSTANCES(O, P, W)                                          \
+  O(2) O(1)                                                             \
+  P(2, 1, false) P(2, 2, false) P(1, 1, false) P(1, 2, false)           \
+  P(2, 1, true) P(2, 2, true) P(1, 1, true) P(1, 2, true)               \
+  W(1, false) W(2, false) W(1, true) W(2, true)
+#define CDD_NONE(...)
+
+namespace cdd {
+// LDS of the 256-thread kernels: what their plans may use (two blocks per
+// CU) and what the launch opts in to
+constexpr int P_LDS_PLAN = 80 * 1024;
+constexpr int P_LDS_MAX = 120 * 1024;
+
+static void opt_in_lds(const void* fn, int bytes) {
+  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            bytes);
+}
+
+// All of them on the first launch of any: set lazily per instantiation, the
+// call could fall into a stream capture.
+static void set_attrs_once() {
   static int attr_done = 0;
   if (attr_done) return;
-  const void* fns[] = {
-      reinterpret_cast<const void*>(&conv_dgrad_direct<2>),
-      reinterpret_cast<const void*>(&conv_dgrad_direct<1>),
-      reinterpret_cast<const void*>(&conv_dgrad_direct_p<2, 1, false>),
-      reinterpret_cast<const void*>(&conv_dgrad_direct_p<2, 2, false>),
-      reinterpret_cast<const void*>(&conv_dgrad_direct_p<1, 1, false>),
-      reinterpret_cast<const void*>(&conv_dgrad_direct_p<1, 2, false>),
-      reinterpret_cast<const void*>(&conv_dgrad_direct_p<2, 1, true>),
-      reinterpret_cast<const void*>(&conv_dgrad_direct_p<2, 2, true>),
-      reinterpret_cast<const void*>(&conv_dgrad_direct_p<1, 1, true>),
-      reinterpret_cast<const void*>(&conv_dgrad_direct_p<1, 2, true>),
-  };
-  for (const void* f : fns)
-    (void)hipFuncSetAttribute(
-        f, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024);
-  const void* wide_fns[] = {
-      reinterpret_cast<const void*>(&conv_dgrad_direct_w<1, false>),
-      reinterpret_cast<const void*>(&conv_dgrad_direct_w<2, false>),
-      reinterpret_cast<const void*>(&conv_dgrad_direct_w<1, true>),
-      reinterpret_cast<const void*>(&conv_dgrad_direct_w<2, true>),
-  };
-  for (const void* f : wide_fns)
-    (void)hipFuncSetAttribute(
-        f, hipFuncAttributeMaxDynamicSharedMemorySize, cdd::W_LDS_MAX);
+#define CDD_ATTR_O(MI_) \
+  opt_in_lds((const void*)&conv_dgrad_direct<MI_>, P_LDS_MAX);
+#define CDD_ATTR_P(MI_, NCT_, PACT_) \
+  opt_in_lds((const void*)&conv_dgrad_direct_p<MI_, NCT_, PACT_>, P_LDS_MAX);
+#define CDD_ATTR_W(NCT_, PACT_) \
+  opt_in_lds((const void*)&conv_dgrad_direct_w<NCT_, PACT_>, W_LDS_MAX);
+  CDD_INSTANCES(CDD_ATTR_O, CDD_ATTR_P, CDD_ATTR_W)
+#undef CDD_ATTR_O
+#undef CDD_ATTR_P
+#undef CDD_ATTR_W
   attr_done = 1;
 }
 
-namespace cdd {
-// host mirror of the per-axis class geometry
-inline void p_axis_window(int pad, int R, int q, int* lo, int* hi) {
-  int t0 = (q + pad) & 1;
-  int nt = (R - t0 + 1) >> 1;
-  int bo = (q + pad - t0) >> 1;
-  *lo = bo - (nt - 1);
-  *hi = bo;
-}
-// region extent along one axis for `len` class pixels: the union of
-// both parities, or (qsplit) the larger single-parity window
-inline int p_axis_extent(int len, int pad, int R, bool qsplit) {
-  int l0, h0, l1, h1;
-  p_axis_window(pad, R, 0, &l0, &h0);
-  p_axis_window(pad, R, 1, &l1, &h1);
-  if (qsplit) return len + std::max(h0 - l0, h1 - l1);
-  return len + std::max(h0, h1) - std::min(l0, l1);
+// A plan asked for an instantiation the table does not have (the plans
+// admit none): say so and launch nothing.
+static void no_instance(const char* kernel, int mi, int nct) {
+  fprintf(stderr, "%s: no instantiation for MI=%d NCT=%d, not launched\n",
+          kernel, mi, nct);
 }
 
-// Persistent kernel eligibility ({} is kind 0: not taken).  On top of the
-// one-shot kernel's conditions: C8 <= 128 (register partials per c-tile),
-// Ko8 a power of two (shift/mask cell decode), and the union region +
-// 32 KiB W double buffer within 80 KiB (two blocks per CU).  Full
-// four-class fusion is preferred; where its region is too large the tile
-// is split by row parity (two classes per staging).
+// ---- plans.  Eligibility ({} is kind 0: not taken).
+// What every direct kernel needs.  R,S >= 2 keeps every parity class's tap
+// set non-empty (ntap >= 1).
+static bool eligible(int H, int W, int C8, int Ko8, long ldw, int R, int S,
+                     int stride) {
+  if (stride != 2 || C8 % 64 != 0 || Ko8 % 128 != 0 || ldw != Ko8)
+    return false;
+  return R >= 2 && S >= 2 && R <= 8 && S <= 8 && !(H & 1) && !(W & 1);
+}
+// On top of it for the persistent kernels: C8 64 or 128 (register partials
+// per c-tile) and Ko8 a power of two (shift/mask cell decode).
+static bool eligible_persistent(int H, int W, int C8, int Ko8, long ldw,
+                                int R, int S, int stride, int pad) {
+  return eligible(H, W, C8, Ko8, ldw, R, S, stride) && C8 > 0 && C8 <= 128 &&
+         (Ko8 & (Ko8 - 1)) == 0 && pad >= 0;
+}
+// a tile of bm class pixels is whole class rows of one image
+static bool tile_fits(int Hc, int Wc, int bm) {
+  return Wc <= bm && bm % Wc == 0 && (Hc * Wc) % bm == 0;
+}
+// The stager's chunk swizzle slot ^ (cc & (co_chunks - 1)) permutes the
+// chunks of a cell if co_chunks is a power of two; otherwise a chunk can
+// come from the next cell.  For the other Ko8 this admits only regions whose
+// columns stay below the lowest set bit of co_chunks: a sufficient condition,
+// not the exact one (with 48 chunks, mask 0b101111, columns 16..31 still
+// permute and the first wrong column is 32), so a few geometries that
+// computed correctly on the one-shot kernel go to dcol + col2im as well.
+static bool swizzle_ok(int Ko8, int rgn_cols) {
+  int co_chunks = Ko8 >> 3;
+  return (co_chunks & (co_chunks - 1)) == 0 ||
+         rgn_cols <= (co_chunks & -co_chunks);
+}
+// Region of a plan: the one-shot kernel stages the window of one class
+// (the larger parity's on each axis), the persistent ones the union of the
+// column parities and of the row parities (qsplit: one row parity).
+struct Region { int rows, cols; };
+static Region plan_region(DgradDirectPlan p, int H, int W, int R, int S,
+                          int pad) {
+  int Hc = H / 2, Wc = W / 2;
+  int rows_c = p.wide ? Hc : p.bm / Wc;
+  return {p_axis_extent(rows_c, pad, R, p.kind == 1 || p.qsplit != 0),
+          p_axis_extent(Wc, pad, S, p.kind == 1)};
+}
+// Fills p.lds_bytes: `imgs` regions + nwbuf W buffers.  False where that
+// exceeds `budget` or the region cannot be staged.
+static bool plan_lds(DgradDirectPlan& p, int H, int W, int Ko8, int R, int S,
+                     int pad, int imgs, int nwbuf, int budget) {
+  Region g = plan_region(p, H, W, R, S, pad);
+  p.lds_bytes = imgs * g.rows * g.cols * Ko8 * 2 + nwbuf * WSLICE_B;
+  return p.lds_bytes <= budget && swizzle_ok(Ko8, g.cols);
+}
+
+// Persistent kernel: the union region + 32 KiB W double buffer within
+// 80 KiB (two blocks per CU).  Full four-class fusion is preferred; where
+// its region is too large the tile is split by row parity (two classes per
+// staging).
 static DgradDirectPlan plan_persistent(int H, int W, int C8, int Ko8,
                                        long ldw, int R, int S, int stride,
                                        int pad) {
-  if (stride != 2 || (C8 != 64 && C8 != 128) || Ko8 % 128 != 0 ||
-      (Ko8 & (Ko8 - 1)) != 0 || ldw != Ko8)
-    return {};
-  if (R < 2 || S < 2 || R > 8 || S > 8 || (H & 1) || (W & 1)) return {};
-  if (pad < 0) return {};
-  int Hc = H / 2, Wc = W / 2;
+  if (!eligible_persistent(H, W, C8, Ko8, ldw, R, S, stride, pad)) return {};
   for (int bm : {128, 64}) {
-    if (Wc > bm || bm % Wc != 0 || (Hc * Wc) % bm != 0) continue;
-    int rows_c = bm / Wc;
+    if (!tile_fits(H / 2, W / 2, bm)) continue;
     for (int qsplit : {0, 1}) {
-      int rgn_rows = p_axis_extent(rows_c, pad, R, qsplit != 0);
-      int rgn_cols = p_axis_extent(Wc, pad, S, false);
-      int lds_b = rgn_rows * rgn_cols * Ko8 * 2 + WBUF_B;
-      if (lds_b > 80 * 1024) continue;
-      return DgradDirectPlan{2, bm, qsplit, lds_b};
+      DgradDirectPlan p{2, bm, qsplit, 0};
+      if (plan_lds(p, H, W, Ko8, R, S, pad, 1, 2, P_LDS_PLAN)) return p;
     }
   }
   return {};
 }
 
-// Wide kernel eligibility: the persistent kernel's conditions on strides,
-// channels, taps and parity; the 8x8 class grid, so that a tile is the
-// class grids of two images; and the tile's full-union regions +
-// three W buffers within the LDS of one CU.  Does not depend on the
-// batch: an odd image count ends in a half tile.
+// Wide kernel: the persistent kernel's conditions; the 8x8 class grid, so
+// that a tile is the class grids of two images; and the tile's full-union
+// regions + three W buffers within the LDS of one CU.  Does not depend on
+// the batch: an odd image count ends in a half tile.
 static DgradDirectPlan plan_wide(int H, int W, int C8, int Ko8, long ldw,
                                  int R, int S, int stride, int pad) {
-  if (stride != 2 || (C8 != 64 && C8 != 128) || Ko8 % 128 != 0 ||
-      (Ko8 & (Ko8 - 1)) != 0 || ldw != Ko8)
-    return {};
-  if (R < 2 || S < 2 || R > 8 || S > 8 || (H & 1) || (W & 1)) return {};
-  if (pad < 0) return {};
-  int Hc = H / 2, Wc = W / 2;
-  const int bm = W_BM;
+  if (!eligible_persistent(H, W, C8, Ko8, ldw, R, S, stride, pad)) return {};
   // the square 8x8 class grid only: the other grids of 64 pixels are
   // neither in the models nor tested
-  if (Hc != 8 || Wc != 8) return {};
-  int rgn_rows = p_axis_extent(Hc, pad, R, false);
-  int rgn_cols = p_axis_extent(Wc, pad, S, false);
-  int lds_b = (bm / (Hc * Wc)) * rgn_rows * rgn_cols * Ko8 * 2 +
-              W_NBUF * WSLICE_B;
-  if (lds_b > W_LDS_MAX) return {};
-  return DgradDirectPlan{2, bm, 0, lds_b, 1};
+  if (H != 16 || W != 16) return {};
+  DgradDirectPlan p{2, W_BM, 0, 0, 1};
+  if (plan_lds(p, H, W, Ko8, R, S, pad, W_BM / 64, W_NBUF, W_LDS_MAX))
+    return p;
+  return {};
 }
 
+// One-shot kernel.  Capped at 2 blocks/CU (160 KiB LDS): 1-block/CU shapes
+// measured slower than their dcol path (stage latency unhidden).
 static DgradDirectPlan plan_oneshot(int H, int W, int C8, int Ko8, long ldw,
-                                    int R, int S, int stride) {
-  if (stride != 2 || C8 % 64 != 0 || Ko8 % 128 != 0 || ldw != Ko8)
-    return {};
-  // R,S >= 2 keeps every parity class's tap set non-empty (Rc,Sc >= 1)
-  if (R < 2 || S < 2 || R > 8 || S > 8 || (H & 1) || (W & 1)) return {};
-  int Hc = H / 2, Wc = W / 2;
+                                    int R, int S, int stride, int pad) {
+  if (!eligible(H, W, C8, Ko8, ldw, R, S, stride)) return {};
   for (int bm : {128, 64}) {
-    if (Wc > bm || bm % Wc != 0 || (Hc * Wc) % bm != 0) continue;
-    int rows_c = bm / Wc;
-    int rgn_rows = rows_c + ((R + 1) >> 1) - 1;
-    int rgn_cols = Wc + ((S + 1) >> 1) - 1;
-    // cap at 2 blocks/CU (160 KiB LDS): 1-block/CU shapes measured
-    // slower than their dcol path (stage latency unhidden)
-    int lds_b = rgn_rows * rgn_cols * Ko8 * 2 + WBUF_B;
-    if (lds_b > 80 * 1024) continue;
-    return DgradDirectPlan{1, bm, 0, lds_b};
+    if (!tile_fits(H / 2, W / 2, bm)) continue;
+    DgradDirectPlan p{1, bm, 0, 0};
+    if (plan_lds(p, H, W, Ko8, R, S, pad, 1, 2, P_LDS_PLAN)) return p;
   }
   return {};
 }
@@ -1311,107 +924,98 @@ static int device_cus() {
   return ncu;
 }
 
-// Grid = CUs x 2 blocks (queried once), capped by the tile count and by
-// GDLJ_DGRAD_PERSIST_BLOCKS (re-read per call; lets small problems make
-// one block walk several tiles).
-static void launch_persistent(const DgradDirectArgs& a, DgradDirectPlan plan,
-                              hipStream_t s) {
-  const int bm = plan.bm, qsplit = plan.qsplit, lds_b = plan.lds_bytes;
-  int Hc = a.H / 2, Wc = a.W / 2;
-  int rows_c = bm / Wc;
-  int rgn_rows = p_axis_extent(rows_c, a.pad, a.R, qsplit != 0);
-  int rgn_cols = p_axis_extent(Wc, a.pad, a.S, false);
-  cdd_set_attrs_once();
-  long ntiles = (long)a.Nb * Hc * Wc / bm * (qsplit ? 2 : 1);
-  long nblk = std::min<long>(ntiles, (long)device_cus() * 2);
+// Grid of a persistent kernel: blocks_per_cu blocks on every CU (queried
+// once), capped by the tile count and by GDLJ_DGRAD_PERSIST_BLOCKS (re-read
+// per call; lets small problems make one block walk several tiles).
+static long persistent_blocks(long ntiles, int blocks_per_cu) {
+  long nblk = std::min<long>(ntiles, (long)device_cus() * blocks_per_cu);
   if (const char* e = getenv("GDLJ_DGRAD_PERSIST_BLOCKS")) {
     long cap = atol(e);
     if (cap > 0) nblk = std::min(nblk, cap);
   }
-  if (nblk <= 0) return;
-  dim3 grid((unsigned)nblk);
-#define CDD_P_LAUNCH2(MI_, NCT_, PACT_)                                     \
-  hipLaunchKernelGGL((conv_dgrad_direct_p<MI_, NCT_, PACT_>), grid,         \
-                     dim3(256), lds_b, s, (const unsigned short*)a.dy,      \
-                     (const unsigned short*)a.Wt, (unsigned short*)a.dx,    \
-                     (const unsigned short*)a.y0, a.part, a.bias_fwd,       \
-                     a.stats_part, (const unsigned short*)a.zp, a.H, a.W,   \
-                     a.C8, a.Ho, a.Wo, a.Ko8, a.ldw, a.R, a.S, a.pad,       \
-                     a.act, a.slope, Hc, Wc, rgn_rows, rgn_cols,            \
-                     make_fastdiv(Wc), (int)ntiles, qsplit)
-#define CDD_P_LAUNCH(MI_, NCT_)                                             \
-  do {                                                                      \
-    if (a.y0 != nullptr) CDD_P_LAUNCH2(MI_, NCT_, true);                    \
-    else CDD_P_LAUNCH2(MI_, NCT_, false);                                   \
-  } while (0)
-  if (bm == 128 && a.C8 == 64) CDD_P_LAUNCH(2, 1);
-  else if (bm == 128) CDD_P_LAUNCH(2, 2);
-  else if (a.C8 == 64) CDD_P_LAUNCH(1, 1);
-  else CDD_P_LAUNCH(1, 2);
-#undef CDD_P_LAUNCH
-#undef CDD_P_LAUNCH2
+  return nblk;
 }
 
-// Grid = CUs x 1 blocks of 512 threads, capped like launch_persistent.
+// the kernels' leading pointer parameters
+#define CDD_PTR_ARGS(a)                                                     \
+  (const unsigned short*)a.dy, (const unsigned short*)a.Wt,                 \
+      (unsigned short*)a.dx, (const unsigned short*)a.y0, a.part,           \
+      a.bias_fwd, a.stats_part, (const unsigned short*)a.zp
+
+static void launch_persistent(const DgradDirectArgs& a, DgradDirectPlan plan,
+                              hipStream_t s) {
+  const int lds_b = plan.lds_bytes, qsplit = plan.qsplit;
+  const int Hc = a.H / 2, Wc = a.W / 2;
+  const Region g = plan_region(plan, a.H, a.W, a.R, a.S, a.pad);
+  set_attrs_once();
+  long ntiles = (long)a.Nb * Hc * Wc / plan.bm * (qsplit ? 2 : 1);
+  long nblk = persistent_blocks(ntiles, 2);
+  if (nblk <= 0) return;
+  const int mi = plan.bm / 64, nct = a.C8 / 64;
+  const bool pact = a.y0 != nullptr;
+#define CDD_LAUNCH_P(MI_, NCT_, PACT_)                                      \
+  if (mi == MI_ && nct == NCT_ && pact == PACT_) {                          \
+    hipLaunchKernelGGL((conv_dgrad_direct_p<MI_, NCT_, PACT_>),             \
+                       dim3((unsigned)nblk), dim3(256), lds_b, s,           \
+                       CDD_PTR_ARGS(a), a.H, a.W, a.C8, a.Ho, a.Wo, a.Ko8,  \
+                       a.ldw, a.R, a.S, a.pad, a.act, a.slope, Hc, Wc,      \
+                       g.rows, g.cols, make_fastdiv(Wc), (int)ntiles,       \
+                       qsplit);                                             \
+    return;                                                                 \
+  }
+  CDD_INSTANCES(CDD_NONE, CDD_LAUNCH_P, CDD_NONE)
+#undef CDD_LAUNCH_P
+  no_instance("conv_dgrad_direct_p", mi, nct);
+}
+
+// one block of 512 threads per CU
 static void launch_wide(const DgradDirectArgs& a, DgradDirectPlan plan,
                         hipStream_t s) {
-  const int bm = plan.bm, lds_b = plan.lds_bytes;
-  int Hc = a.H / 2, Wc = a.W / 2;
-  int imgs = bm / (Hc * Wc);
-  int rgn_rows = p_axis_extent(Hc, a.pad, a.R, false);
-  int rgn_cols = p_axis_extent(Wc, a.pad, a.S, false);
-  cdd_set_attrs_once();
+  const int lds_b = plan.lds_bytes;
+  const int Hc = a.H / 2, Wc = a.W / 2;
+  const int imgs = plan.bm / (Hc * Wc);
+  const Region g = plan_region(plan, a.H, a.W, a.R, a.S, a.pad);
+  set_attrs_once();
   long ntiles = ((long)a.Nb + imgs - 1) / imgs;
-  long nblk = std::min<long>(ntiles, (long)device_cus());
-  if (const char* e = getenv("GDLJ_DGRAD_PERSIST_BLOCKS")) {
-    long cap = atol(e);
-    if (cap > 0) nblk = std::min(nblk, cap);
-  }
+  long nblk = persistent_blocks(ntiles, 1);
   if (nblk <= 0) return;
-  dim3 grid((unsigned)nblk);
-#define CDD_W_LAUNCH2(NCT_, PACT_)                                          \
-  hipLaunchKernelGGL((conv_dgrad_direct_w<NCT_, PACT_>), grid,              \
-                     dim3(W_THREADS), lds_b, s,                             \
-                     (const unsigned short*)a.dy,                           \
-                     (const unsigned short*)a.Wt, (unsigned short*)a.dx,    \
-                     (const unsigned short*)a.y0, a.part, a.bias_fwd,       \
-                     a.stats_part, (const unsigned short*)a.zp, a.Nb, a.H,  \
-                     a.W, a.C8, a.Ho, a.Wo, a.Ko8, a.ldw, a.R, a.S, a.pad,  \
-                     a.act, a.slope, Hc, Wc, rgn_rows, rgn_cols,            \
-                     make_fastdiv(Wc), (int)ntiles)
-#define CDD_W_LAUNCH(NCT_)                                                  \
-  do {                                                                      \
-    if (a.y0 != nullptr) CDD_W_LAUNCH2(NCT_, true);                         \
-    else CDD_W_LAUNCH2(NCT_, false);                                        \
-  } while (0)
-  if (a.C8 == 64) CDD_W_LAUNCH(1);
-  else CDD_W_LAUNCH(2);
-#undef CDD_W_LAUNCH
-#undef CDD_W_LAUNCH2
+  const int nct = a.C8 / 64;
+  const bool pact = a.y0 != nullptr;
+#define CDD_LAUNCH_W(NCT_, PACT_)                                           \
+  if (nct == NCT_ && pact == PACT_) {                                       \
+    hipLaunchKernelGGL((conv_dgrad_direct_w<NCT_, PACT_>),                  \
+                       dim3((unsigned)nblk), dim3(W_THREADS), lds_b, s,     \
+                       CDD_PTR_ARGS(a), a.Nb, a.H, a.W, a.C8, a.Ho, a.Wo,   \
+                       a.Ko8, a.ldw, a.R, a.S, a.pad, a.act, a.slope, Hc,   \
+                       Wc, g.rows, g.cols, make_fastdiv(Wc), (int)ntiles);  \
+    return;                                                                 \
+  }
+  CDD_INSTANCES(CDD_NONE, CDD_NONE, CDD_LAUNCH_W)
+#undef CDD_LAUNCH_W
+  no_instance("conv_dgrad_direct_w", 2, nct);
 }
 
 static void launch_oneshot(const DgradDirectArgs& a, DgradDirectPlan plan,
                            hipStream_t s) {
-  const int bm = plan.bm, lds_b = plan.lds_bytes;
-  int Hc = a.H / 2, Wc = a.W / 2;
-  int rows_c = bm / Wc;
-  int rgn_rows = rows_c + ((a.R + 1) >> 1) - 1;
-  int rgn_cols = Wc + ((a.S + 1) >> 1) - 1;
-  cdd_set_attrs_once();
-  dim3 grid((long)a.Nb * Hc * Wc / bm, a.C8 / 64, 4);
-#define CDD_LAUNCH(MI_)                                                     \
-  hipLaunchKernelGGL((conv_dgrad_direct<MI_>), grid, dim3(256), lds_b, s,   \
-                     (const unsigned short*)a.dy,                           \
-                     (const unsigned short*)a.Wt, (unsigned short*)a.dx,    \
-                     (const unsigned short*)a.y0, a.part, a.bias_fwd,       \
-                     a.stats_part, (const unsigned short*)a.zp, a.Nb, a.H,  \
-                     a.W, a.C8, a.Ho, a.Wo, a.Ko8, a.ldw, a.R, a.S, a.pad,  \
-                     a.act, a.slope, Hc, Wc, rows_c, rgn_rows, rgn_cols,    \
-                     make_fastdiv(Wc))
-  if (bm == 128) CDD_LAUNCH(2);
-  else CDD_LAUNCH(1);
-#undef CDD_LAUNCH
+  const int lds_b = plan.lds_bytes;
+  const int Hc = a.H / 2, Wc = a.W / 2;
+  const Region g = plan_region(plan, a.H, a.W, a.R, a.S, a.pad);
+  set_attrs_once();
+  dim3 grid((long)a.Nb * Hc * Wc / plan.bm, a.C8 / 64, 4);
+  const int mi = plan.bm / 64;
+#define CDD_LAUNCH_O(MI_)                                                   \
+  if (mi == MI_) {                                                          \
+    hipLaunchKernelGGL((conv_dgrad_direct<MI_>), grid, dim3(256), lds_b, s, \
+                       CDD_PTR_ARGS(a), a.Nb, a.H, a.W, a.C8, a.Ho, a.Wo,   \
+                       a.Ko8, a.ldw, a.R, a.S, a.pad, a.act, a.slope, Hc,   \
+                       Wc, g.rows, g.cols, make_fastdiv(Wc));               \
+    return;                                                                 \
+  }
+  CDD_INSTANCES(CDD_LAUNCH_O, CDD_NONE, CDD_NONE)
+#undef CDD_LAUNCH_O
+  no_instance("conv_dgrad_direct", mi, 0);
 }
+#undef CDD_PTR_ARGS
 }  // namespace cdd
 
 extern "C" {
@@ -1445,7 +1049,7 @@ DgradDirectPlan conv_dgrad_direct_plan(int H, int W, int C8, int Ko8,
         cdd::plan_persistent(H, W, C8, Ko8, ldw, R, S, stride, pad);
     if (p.kind != 0) return p;
   }
-  return cdd::plan_oneshot(H, W, C8, Ko8, ldw, R, S, stride);
+  return cdd::plan_oneshot(H, W, C8, Ko8, ldw, R, S, stride, pad);
 }
 
 void launch_conv_dgrad_direct(const DgradDirectArgs& a, DgradDirectPlan plan,

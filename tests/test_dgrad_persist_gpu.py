@@ -1,7 +1,11 @@
 """GPU numerics of the persistent class-fused direct dgrad / convT kernel
 (conv_dgrad_direct_p in conv_dgrad_direct.hip).
 
-Every case runs the persistent kernel (GDLJ_DGRAD_PERSIST=1, the default)
+Every case runs the default routing (GDLJ_DGRAD_PERSIST=1; the other gates
+are left unset, so the 8x8-class-grid cases run the wide kernel
+conv_dgrad_direct_w and the rest the persistent one; the persistent kernel
+on the 8x8 grid, its qsplit path, is pinned by
+test_dgrad_direct_golden_gpu.py and compared in test_dgrad_wide_gpu.py)
 with the grid capped at 1 block (one block walks every tile), 3 blocks
 (uneven split) and uncapped, and compares against the one-shot kernel
 (GDLJ_DGRAD_PERSIST=0).  dx / y must be bit-identical: per output element
@@ -11,55 +15,29 @@ reference the project's bounds for these paths apply.
 """
 
 import functools
-import os
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+import dgrad_direct_cases as D
+from dgrad_direct_cases import (DEV, convt_case, dgrad_case, mk, p_eligible,
+                                relerr, run_dgrad)
+
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 CAPS = [1, 3, None]
 
 
-def mk(shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randn(*shape, generator=g) * scale
-    return t.to(DEV, torch.bfloat16)
-
-
-def relerr(a, b):
-    a = a.float().cpu()
-    b = b.float().cpu()
-    denom = b.abs().max().clamp_min(1e-6)
-    return ((a - b).abs().max() / denom).item()
-
-
 def with_env(persist, cap, fn):
-    """Run fn() with the two routing switches set, then restore them."""
-    keys = ("GDLJ_DGRAD_PERSIST", "GDLJ_DGRAD_PERSIST_BLOCKS")
-    old = {k: os.environ.get(k) for k in keys}
-    os.environ["GDLJ_DGRAD_PERSIST"] = persist
-    if cap is None:
-        os.environ.pop("GDLJ_DGRAD_PERSIST_BLOCKS", None)
-    else:
-        os.environ["GDLJ_DGRAD_PERSIST_BLOCKS"] = str(cap)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def p_eligible(h, c8, ko8, r, pad):
-    from gan_deeplearning4j_amd.ops.backend import hip_ext
-
-    return hip_ext().conv_dgrad_direct_p_eligible(h, h, c8, ko8, ko8, r, r,
-                                                  2, pad)
+    """Run fn() with GDLJ_DGRAD_PERSIST = persist and the grid cap, every
+    other routing gate unset: "1" is the default routing, i.e. the wide
+    kernel where it takes the geometry, else the persistent one.
+    Deliberately unlike this file's earlier helper, which left
+    GDLJ_DGRAD_WIDE and GDLJ_DGRAD_DIRECT as the caller's environment had
+    them: an exported gate no longer changes which kernels these tests
+    compare."""
+    return D.with_env({"GDLJ_DGRAD_PERSIST": persist}, cap, fn)
 
 
 # ------------------------------------------------------------ conv2d dgrad
@@ -72,27 +50,6 @@ DGRAD_SHAPES = [
     (4, 128, 32, 128, 4, 1),   # BM=128 with two c-tiles
     (4, 64, 32, 128, 7, 3),    # large taps: BM=64 tile, one c-tile
 ]
-
-
-@functools.lru_cache(maxsize=None)
-def dgrad_case(nb, cin, h, cout, r, pad):
-    x = mk((nb, cin, h, h), 50, 0.5)
-    w = mk((cout, cin, r, r), 51, 0.2)
-    ho = (h + 2 * pad - r) // 2 + 1
-    gout = mk((nb, cout, ho, ho), 52)
-    xr = x.float().cpu().requires_grad_(True)
-    F.conv2d(xr, w.float().cpu(), None, stride=2, padding=pad).backward(
-        gout.float().cpu())
-    return x, w, gout, xr.grad
-
-
-def run_dgrad(x, w, gout, pad):
-    from gan_deeplearning4j_amd.ops import gpu_ops
-
-    x2 = x.detach().clone().requires_grad_(True)
-    y = gpu_ops.conv2d(x2, w, None, 2, pad, "identity")
-    y.backward(gout)
-    return x2.grad
 
 
 @pytest.mark.parametrize("cap", CAPS)
@@ -114,25 +71,13 @@ CONVT_SHAPES = [
 ]
 
 
-@functools.lru_cache(maxsize=None)
-def convt_case(cin, hi, cout, r, pad):
-    x = mk((4, cin, hi, hi), 80, 0.5)
-    w = mk((cin, cout, r, r), 81, 0.1)
-    b = torch.randn(cout, generator=torch.Generator().manual_seed(84)).to(
-        DEV, torch.bfloat16)
-    ref = torch.tanh(F.conv_transpose2d(
-        x.float().cpu(), w.float().cpu(), b.float().cpu(), stride=2,
-        padding=pad))
-    return x, w, b, ref
-
-
 @pytest.mark.parametrize("cap", CAPS)
 @pytest.mark.parametrize("cin,hi,cout,r,pad", CONVT_SHAPES)
 def test_convt_persist_matches_oneshot(cin, hi, cout, r, pad, cap):
     from gan_deeplearning4j_amd.ops import gpu_ops
 
     assert p_eligible(2 * hi, cout, cin, r, pad) != 0
-    x, w, b, ref = convt_case(cin, hi, cout, r, pad)
+    x, w, b, ref = convt_case(4, cin, hi, cout, r, pad)
 
     def run():
         return gpu_ops.conv_transpose2d(x, w, b, 2, pad, "tanh")
@@ -253,6 +198,31 @@ def test_dgrad_persist_refuses_lds_overflow():
     x, w, gout, ref = dgrad_case(nb, cin, h, cout, r, pad)
     dx = with_env("1", None, lambda: run_dgrad(x, w, gout, pad))
     assert relerr(dx, ref) < 0.04
+
+
+def test_dgrad_oneshot_refuses_unswizzlable_region():
+    # Ko8 = 384 is 48 16-byte chunks per cell, not a power of two: the
+    # stager's chunk swizzle slot ^ (cc & 47) stops being a permutation of
+    # a cell's chunks at region column 32.  The plan refuses such Ko8 by the
+    # simple sufficient condition "more columns than the lowest set bit of
+    # 48", i.e. from 17 columns on.  This geometry (2x32 class grid, 2x2
+    # taps: a 2x32 region of 48 KiB, which fits) has 32 columns: its staging
+    # would still be right, but it is on the refused side of that condition,
+    # so no direct kernel may take it and the empty result sends the caller
+    # to dcol + col2im.  dpre is the head of a larger buffer.
+    from gan_deeplearning4j_amd.ops import gpu_ops
+    from gan_deeplearning4j_amd.ops.backend import hip_ext
+
+    n, h, w, c8, ko8, r = 1, 4, 64, 64, 384, 2
+    ho, wo = h // 2, w // 2
+    rows = n * ho * wo
+    buf = mk((rows + 8, ko8), 95)
+    dpre = buf[:rows]
+    wt = mk((r * r * c8, ko8), 96, 0.2)
+    zp = gpu_ops._zero_page(dpre.device)
+    res = D.with_env(D.ONESHOT, None, lambda: hip_ext().conv_dgrad_direct(
+        dpre, wt, None, zp, n, h, w, c8, ho, wo, r, r, 2, 0, 0, 0.0, False))
+    assert len(res) == 0
 
 
 # ----------------------------------------------------------------- capture

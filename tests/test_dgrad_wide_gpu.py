@@ -18,61 +18,18 @@ fp32 torch reference the project's bounds for these paths apply.
 """
 
 import functools
-import os
 
 import pytest
 import torch
-import torch.nn.functional as F
+
+import dgrad_direct_cases as D
+from dgrad_direct_cases import (DCOL, ONESHOT, WIDE, WIDE0, mk, p_eligible,
+                                relerr, run_dgrad, run_pact, with_env)
 
 gpu = pytest.mark.gpu
 
-DEV = "cuda:0"
 NB = 3
 CAPS = [1, 2, None]
-GATES = ("GDLJ_DGRAD_DIRECT", "GDLJ_DGRAD_PERSIST", "GDLJ_DGRAD_WIDE",
-         "GDLJ_DGRAD_PERSIST_BLOCKS")
-WIDE = {}                                  # the default routing
-WIDE0 = {"GDLJ_DGRAD_WIDE": "0"}
-ONESHOT = {"GDLJ_DGRAD_PERSIST": "0"}
-DCOL = {"GDLJ_DGRAD_DIRECT": "0"}
-
-
-def mk(shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    t = torch.randn(*shape, generator=g) * scale
-    return t.to(DEV, torch.bfloat16)
-
-
-def relerr(a, b):
-    a = a.float().cpu()
-    b = b.float().cpu()
-    denom = b.abs().max().clamp_min(1e-6)
-    return ((a - b).abs().max() / denom).item()
-
-
-def with_env(env, cap, fn):
-    """Run fn() with exactly the given routing gates set, then restore."""
-    old = {k: os.environ.get(k) for k in GATES}
-    for k in GATES:
-        os.environ.pop(k, None)
-    os.environ.update(env)
-    if cap is not None:
-        os.environ["GDLJ_DGRAD_PERSIST_BLOCKS"] = str(cap)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def p_eligible(h, c8, ko8, r, pad):
-    from gan_deeplearning4j_amd.ops.backend import hip_ext
-
-    return hip_ext().conv_dgrad_direct_p_eligible(h, h, c8, ko8, ko8, r, r,
-                                                  2, pad)
 
 
 # ------------------------------------------------------------ conv2d dgrad
@@ -94,25 +51,8 @@ def want_kind(h):
     return 2 if h == 16 else 1
 
 
-@functools.lru_cache(maxsize=None)
 def dgrad_case(cin, h, cout, r, pad):
-    x = mk((NB, cin, h, h), 50, 0.5)
-    w = mk((cout, cin, r, r), 51, 0.2)
-    ho = (h + 2 * pad - r) // 2 + 1
-    gout = mk((NB, cout, ho, ho), 52)
-    xr = x.float().cpu().requires_grad_(True)
-    F.conv2d(xr, w.float().cpu(), None, stride=2, padding=pad).backward(
-        gout.float().cpu())
-    return x, w, gout, xr.grad
-
-
-def run_dgrad(x, w, gout, pad):
-    from gan_deeplearning4j_amd.ops import gpu_ops
-
-    x2 = x.detach().clone().requires_grad_(True)
-    y = gpu_ops.conv2d(x2, w, None, 2, pad, "identity")
-    y.backward(gout)
-    return x2.grad
+    return D.dgrad_case(NB, cin, h, cout, r, pad)
 
 
 @functools.lru_cache(maxsize=None)
@@ -157,17 +97,8 @@ CONVT_SHAPES = [
 
 @functools.lru_cache(maxsize=None)
 def convt_case(cin, hi, cout, r, pad):
-    from gan_deeplearning4j_amd.ops import gpu_ops
-
-    x = mk((NB, cin, hi, hi), 80, 0.5)
-    w = mk((cin, cout, r, r), 81, 0.1)
-    b = torch.randn(cout, generator=torch.Generator().manual_seed(84)).to(
-        DEV, torch.bfloat16)
-    ref = torch.tanh(F.conv_transpose2d(
-        x.float().cpu(), w.float().cpu(), b.float().cpu(), stride=2,
-        padding=pad))
-    y0 = with_env(WIDE0, None,
-                  lambda: gpu_ops.conv_transpose2d(x, w, b, 2, pad, "tanh"))
+    x, w, b, ref = D.convt_case(NB, cin, hi, cout, r, pad)
+    y0 = with_env(WIDE0, None, lambda: D.run_convt(x, w, b, pad))
     return x, w, b, ref, y0
 
 
@@ -229,23 +160,8 @@ PACT_SHAPES = [
 
 @functools.lru_cache(maxsize=None)
 def pact_case(cin, h, cout):
-    xa = F.leaky_relu(mk((NB, cin, h, h), 60, 0.5), 0.2)
-    w = mk((cout, cin, 4, 4), 61, 0.2)
-    gout = mk((NB, cout, h // 2, h // 2), 62)
+    xa, w, gout = D.pact_inputs(NB, cin, h, cout)
     return xa, w, gout, with_env(WIDE0, None, lambda: run_pact(xa, w, gout))
-
-
-def run_pact(xa, w, gout):
-    from gan_deeplearning4j_amd.ops import gpu_ops
-    from gan_deeplearning4j_amd.ops.gpu_ops import take_act_fused
-
-    got = []
-    x = xa.detach().clone().requires_grad_(True)
-    x.register_hook(lambda g: got.append(take_act_fused(g)))
-    y = gpu_ops.conv2d(x, w, None, 2, 1, "identity", prev_act=(3, 0.2, True))
-    y.backward(gout)
-    assert got and got[0] is not None and got[0][2] is not None
-    return x.grad, got[0][2].float().cpu()
 
 
 @gpu
