@@ -1026,18 +1026,29 @@ extern "C" {
 // GDLJ_DGRAD_WIDE=0 sends the geometries of the wide kernel back to the
 // two-blocks-per-CU persistent kernel (or, where that one does not take
 // them, to the caller's fallback).  The result is the plan's allow mask:
-// kDgradAllowPersist | kDgradAllowWide, or 0 for the one-shot kernel.
+// kDgradAllowPersist | kDgradAllowWide, or 0 for the one-shot kernel, each
+// with kDgradAllowClassGemm or without.
 int conv_dgrad_direct_allow() {
   auto off = [](const char* name) {
     const char* e = getenv(name);
     return e != nullptr && e[0] == '0' && e[1] == '\0';
   };
-  if (off("GDLJ_DGRAD_PERSIST")) return 0;
-  return off("GDLJ_DGRAD_WIDE") ? kDgradAllowPersist
-                                : kDgradAllowPersist | kDgradAllowWide;
+  // GDLJ_DGRAD_CLASSGEMM=0 leaves what no direct kernel takes to the caller's
+  // fallback (dcol + col2im); it does not depend on the other two gates.
+  // GDLJ_DGRAD_CLASSGEMM_FP32=1: one fp32 accumulation over all taps on the
+  // 256-wide tile (faster and more accurate, but not the bits of dcol +
+  // col2im, which the default reproduces)
+  const char* f32 = getenv("GDLJ_DGRAD_CLASSGEMM_FP32");
+  const int cls = off("GDLJ_DGRAD_CLASSGEMM") ? 0
+                  : kDgradAllowClassGemm |
+                        (f32 != nullptr && f32[0] == '1' ? kDgradClassFp32 : 0);
+  if (off("GDLJ_DGRAD_PERSIST")) return cls;
+  return cls | (off("GDLJ_DGRAD_WIDE")
+                    ? kDgradAllowPersist
+                    : kDgradAllowPersist | kDgradAllowWide);
 }
 
-DgradDirectPlan conv_dgrad_direct_plan(int H, int W, int C8, int Ko8,
+DgradDirectPlan conv_dgrad_direct_plan(int Nb, int H, int W, int C8, int Ko8,
                                        long ldw, int R, int S, int stride,
                                        int pad, int allow) {
   if ((allow & kDgradAllowPersist) && (allow & kDgradAllowWide)) {
@@ -1049,7 +1060,13 @@ DgradDirectPlan conv_dgrad_direct_plan(int H, int W, int C8, int Ko8,
         cdd::plan_persistent(H, W, C8, Ko8, ldw, R, S, stride, pad);
     if (p.kind != 0) return p;
   }
-  return cdd::plan_oneshot(H, W, C8, Ko8, ldw, R, S, stride, pad);
+  DgradDirectPlan p = cdd::plan_oneshot(H, W, C8, Ko8, ldw, R, S, stride, pad);
+  if (p.kind != 0) return p;
+  // last resort: one gathered 8-phase GEMM per parity class (gemm8p.hip)
+  if ((allow & kDgradAllowClassGemm) &&
+      conv_dgrad_classgemm_eligible(Nb, H, W, C8, Ko8, ldw, R, S, stride, pad))
+    return DgradDirectPlan{(allow & kDgradClassFp32) ? 4 : 3, 0, 0, 0, 0};
+  return {};
 }
 
 void launch_conv_dgrad_direct(const DgradDirectArgs& a, DgradDirectPlan plan,
@@ -1057,6 +1074,8 @@ void launch_conv_dgrad_direct(const DgradDirectArgs& a, DgradDirectPlan plan,
   if (plan.kind == 2 && plan.wide) cdd::launch_wide(a, plan, s);
   else if (plan.kind == 2) cdd::launch_persistent(a, plan, s);
   else if (plan.kind == 1) cdd::launch_oneshot(a, plan, s);
+  else if (plan.kind >= 3)
+    launch_conv_dgrad_classgemm(a, plan.kind == 4, s);
 }
 
 }  // extern "C"

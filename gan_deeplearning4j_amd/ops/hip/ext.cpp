@@ -309,9 +309,23 @@ DgradDirectArgs dgrad_direct_args(int64_t N, int64_t H, int64_t W, int64_t C8,
 }
 
 DgradDirectPlan dgrad_direct_plan(const DgradDirectArgs& a, int64_t stride) {
-  return conv_dgrad_direct_plan(a.H, a.W, a.C8, a.Ko8, a.ldw, a.R, a.S,
+  return conv_dgrad_direct_plan(a.Nb, a.H, a.W, a.C8, a.Ko8, a.ldw, a.R, a.S,
                                 (int)stride, a.pad,
                                 conv_dgrad_direct_allow());
+}
+
+// The class GEMMs (kind 3 / 4) have no fused act backward: with y0 the
+// caller's dcol + col2im_dact path keeps the geometry.
+// The class GEMMs derive each class grid from H, W alone: the dy / x grid
+// must be the one a stride-2 conv of that geometry produces.
+static void check_class_grid(const DgradDirectArgs& a) {
+  TORCH_CHECK(a.Ho == (a.H + 2 * a.pad - a.R) / 2 + 1 &&
+                  a.Wo == (a.W + 2 * a.pad - a.S) / 2 + 1,
+              "class GEMM: Ho, Wo do not match H, W, R, S, pad at stride 2");
+}
+
+static bool has_y0(const c10::optional<torch::Tensor>& y0) {
+  return y0.has_value() && y0->defined();
 }
 
 // Direct parity-decomposed strided dgrad (conv_dgrad_direct.hip):
@@ -330,13 +344,14 @@ std::vector<torch::Tensor> conv_dgrad_direct(
   DgradDirectArgs a = dgrad_direct_args(N, H, W, C8, Ho, Wo, dpre.size(1),
                                         wt.size(1), R, S, pad, act, slope);
   DgradDirectPlan plan = dgrad_direct_plan(a, stride);
-  if (plan.kind == 0) return {};
+  if (plan.kind == 0 || (plan.kind >= 3 && has_y0(y0))) return {};
+  if (plan.kind >= 3) check_class_grid(a);
   TORCH_CHECK(dpre.size(0) == N * Ho * Wo, "dpre rows");
   TORCH_CHECK(wt.size(0) >= R * S * C8, "wt rows");
   auto st = cur_stream();
   torch::Tensor out = torch::empty({N, H, W, C8}, dpre.options());
   torch::Tensor part, db;
-  if (y0.has_value() && y0->defined()) {
+  if (has_y0(y0)) {
     check_bf16(*y0, "y0");
     TORCH_CHECK(y0->numel() == N * H * W * C8, "y0 shape");
     a.y0 = y0->data_ptr();
@@ -378,7 +393,11 @@ std::vector<torch::Tensor> conv_transpose_fwd_direct(
   DgradDirectArgs a = dgrad_direct_args(N, Ho, Wo, Co8, Hi, Wi, x2d.size(1),
                                         w2a.size(1), R, S, pad, act, slope);
   DgradDirectPlan plan = dgrad_direct_plan(a, stride);
-  if (plan.kind == 0) return {};
+  // kind 3 reproduces dcol + col2im bit for bit, and col2im_stats sums the
+  // unrounded y, which a pass over the stored bf16 y cannot reproduce (kind 4
+  // makes no such promise and runs that pass)
+  if (plan.kind == 0 || (plan.kind == 3 && want_stats)) return {};
+  if (plan.kind >= 3) check_class_grid(a);
   TORCH_CHECK(x2d.size(0) == N * Hi * Wi, "x2d rows");
   TORCH_CHECK(w2a.size(0) >= R * S * Co8, "w2a rows");
   auto st = cur_stream();
@@ -394,8 +413,10 @@ std::vector<torch::Tensor> conv_transpose_fwd_direct(
   torch::Tensor part, ssum, ssq;
   if (want_stats) {
     auto f32 = x2d.options().dtype(torch::kFloat32);
-    part = torch::zeros({kPartRows, 2 * Co8}, f32);
-    a.stats_part = part.data_ptr<float>();
+    // kind 4: a pass over y fills part
+    part = plan.kind == 4 ? torch::empty({kPartRows, 2 * Co8}, f32)
+                          : torch::zeros({kPartRows, 2 * Co8}, f32);
+    if (plan.kind != 4) a.stats_part = part.data_ptr<float>();
     ssum = torch::empty({Co8}, f32);
     ssq = torch::empty({Co8}, f32);
   }
@@ -404,6 +425,13 @@ std::vector<torch::Tensor> conv_transpose_fwd_direct(
   a.dx = y.data_ptr();
   a.zp = zero_page.data_ptr();
   launch_conv_dgrad_direct(a, plan, st);
+  if (want_stats && plan.kind == 4) {
+    int gx = launch_bn_stats_part(y.data_ptr(), (long)(N * Ho * Wo),
+                                  (int)Co8, part.data_ptr<float>(), st);
+    launch_bn_stats_sum2(part.data_ptr<float>(), gx, (int)Co8,
+                         ssum.data_ptr<float>(), ssq.data_ptr<float>(), st);
+    return {y, ssum, ssq};
+  }
   if (a.stats_part != nullptr) {
     launch_bn_stats_sum2(a.stats_part, kPartRows, (int)Co8,
                          ssum.data_ptr<float>(), ssq.data_ptr<float>(), st);
@@ -1037,8 +1065,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("conv_dgrad_direct_p_eligible",
           [](int64_t H, int64_t W, int64_t C8, int64_t Ko8, int64_t ldw,
              int64_t R, int64_t S, int64_t stride, int64_t pad) {
+            // no batch, no class-GEMM bit: this asks about kind 2 only
             DgradDirectPlan p = conv_dgrad_direct_plan(
-                (int)H, (int)W, (int)C8, (int)Ko8, (long)ldw, (int)R, (int)S,
+                0, (int)H, (int)W, (int)C8, (int)Ko8, (long)ldw, (int)R, (int)S,
                 (int)stride, (int)pad, kDgradAllowPersist | kDgradAllowWide);
             return p.kind != 2 ? 0 : p.wide ? 2 : 1;
           },

@@ -44,8 +44,9 @@
 // so the glds count per phase is constant and the vmcnt immediates exact.
 //
 // GATHER_A = implicit-GEMM convolution (ConvGather modes 0 fwd /
-// 1 transposed / 2 parity-class with output scatter); B (weights) is
-// always a plain K-contiguous operand.
+// 1 transposed / 2 parity-class with output scatter); B (weights) is a
+// plain K-contiguous operand, or with TAPB (mode 2 only) the tap-major
+// [(r,s,c)][ko] pack read in place, see p8::TapSlice.
 //
 // DEEP (BNT=256 only): two counted waits per K-tile at depth 3 regions —
 // measured neutral-to-negative (profiles/gemm8p_ab.md), kept env-gated.
@@ -179,6 +180,46 @@ DEV_INLINE bf16x8 frag(const char* opb, int rowblk, int kc, int fr, int fq) {
                           (((fq ^ swz<SWZ>(fr)) & 3) << 4));
 }
 
+// Tap-sliced B (TAPB): the GEMM is one parity class of a strided transposed
+// conv (ConvGather mode 2) and B is not a per-class [n][(r2,s2,ko)] pack but
+// the [(r,s,c)][ko] pack the direct dgrad bindings hold, read in place: the
+// row of output channel n for K-tile kt is
+//   B + ((tap_rs(kt) * N + n) * ldb) + ko0(kt),
+//   tap_rs = (prh + stride*r2) * S + (prw + stride*s2),
+// in the K order (r2, s2, ko) k_decode gives the A side (ga.R, ga.S = the
+// class's tap counts, ga.C = Ko8).  Ko8 % BK == 0, so a K-tile never
+// straddles a tap.  The position is wave-uniform and moves only between
+// K-tiles: a cursor stepped by compare-and-reset, no division.
+struct TapSlice {
+  int S;         // full kernel width
+  int prh, prw;  // first tap of the class on each axis
+};
+
+struct TapCursor {
+  long base;  // element offset of the tap's channel-0 row
+  int ko0;    // first ko of the K-tile inside the tap
+  int r2, s2;
+};
+
+DEV_INLINE long tap_base(const TapSlice& ts, const ConvGather& g, int r2,
+                         int s2, int N, long ldb) {
+  int rs = (ts.prh + g.stride * r2) * ts.S + ts.prw + g.stride * s2;
+  return (long)rs * N * ldb;
+}
+
+DEV_INLINE void tap_next(TapCursor& c, const TapSlice& ts,
+                         const ConvGather& g, int N, long ldb) {
+  c.ko0 += BK;
+  if (c.ko0 == g.C) {
+    c.ko0 = 0;
+    if (++c.s2 == g.S) {
+      c.s2 = 0;
+      ++c.r2;
+    }
+    c.base = tap_base(ts, g, c.r2, c.s2, N, ldb);
+  }
+}
+
 }  // namespace p8
 
 // TWEAK bits (within-probe A/B candidates, tools/ab_gemm8p.py):
@@ -190,13 +231,24 @@ DEV_INLINE bf16x8 frag(const char* opb, int rowblk, int kc, int fr, int fq) {
 // +4.9% within-probe over the flip form at square-4k (tools/ab_gemm8p.py:
 // 1188 -> 1247 TF median of 12 interleaved rounds; n-major decomposition
 // -2.2%, partial lgkm +0.5% noise) — it is the production default below.
-template <bool GATHER_A, int SWZ, bool DEEP, int BNT = 256, int TWEAK = 2>
+//
+// TAPB != 0 (needs GATHER_A, ga.mode == 2): B is tap-sliced, see
+// p8::TapSlice.  A gathered A has no row pitch, so lda carries the one number
+// ga does not hold, the full kernel width S; the kernel's signature stays
+// what it was.  TAPB == 1 accumulates all taps in fp32.  TAPB == 2 (BNT = 128:
+// it keeps a second accumulator set) rounds every tap's sum to bf16 and adds
+// the taps in fp32, which is bit for bit what dcol GEMM + col2im computes.
+template <bool GATHER_A, int SWZ, bool DEEP, int BNT = 256, int TWEAK = 2,
+          int TAPB = 0>
 __global__ __launch_bounds__(512, 2) void gemm_tn_8p(
     const unsigned short* __restrict__ A, const unsigned short* __restrict__ B,
     unsigned short* __restrict__ C, const float* __restrict__ bias, int M,
     int N, int K, long lda, long ldb, int act, float slope, ConvGather ga,
     const unsigned short* __restrict__ zp) {
   using namespace p8;
+  static_assert(!TAPB || GATHER_A, "tap-sliced B goes with a gathered A");
+  constexpr bool TAPR = TAPB == 2;  // per-tap bf16 rounding
+  static_assert(!TAPR || BNT == 128, "no registers for tot at BNT = 256");
   constexpr int OPTB = BNT * BK * 2;
   constexpr int BUF = OPTA + OPTB;
   constexpr int MI = (BNT == 256) ? 8 : 4;   // per-wave M fragments
@@ -225,6 +277,12 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_8p(
   const int fr = lane & 15, fq = lane >> 4;
 
   f32x4 acc[MI][4];
+  f32x4 tot[TAPR ? MI : 1][4];  // TAPR: sum of the finished taps
+  int tap_k = 0;                // TAPR: k of the running tile inside its tap
+  #pragma unroll
+  for (int i = 0; i < (TAPR ? MI : 1); ++i)
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) tot[i][j] = {0.f, 0.f, 0.f, 0.f};
   #pragma unroll
   for (int i = 0; i < MI; ++i)
     #pragma unroll
@@ -244,22 +302,40 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_8p(
     else
       stage_a_plain<SWZ, BNT>(A, m0, M, lda, tc * BK, mih, abuf(tc));
   };
-  auto stage_b = [&](int tt, int nih) {
+  // TAPB: cur is the cursor of K-tile min(tt, ntiles - 1)
+  auto stage_b = [&](int tt, int nih, const TapCursor& cur) {
     int tc = min(tt, ntiles - 1);
-    stage_b_plain<SWZ, BNT>(B, n0, N, ldb, tc * BK, nih, bbuf(tc));
+    if (TAPB)
+      stage_b_plain<SWZ, BNT>(B + cur.base, n0, N, ldb, cur.ko0, nih,
+                              bbuf(tc));
+    else
+      stage_b_plain<SWZ, BNT>(B, n0, N, ldb, tc * BK, nih, bbuf(tc));
   };
+  // cursors of K-tiles 0, min(t+1, ntiles-1), min(t+2, ntiles-1)
+  TapCursor c0{}, c1{}, c2{};
+  TapSlice ts{};
+  if (TAPB) {
+    ts.S = (int)lda;
+    ts.prh = (ga.oqh + ga.pad) % ga.stride;
+    ts.prw = (ga.oqw + ga.pad) % ga.stride;
+    c0.base = tap_base(ts, ga, 0, 0, N, ldb);
+    c1 = c0;
+    if (ntiles > 1) tap_next(c1, ts, ga, N, ldb);
+    c2 = c1;
+    if (ntiles > 2) tap_next(c2, ts, ga, N, ldb);
+  }
 
   // prologue: all of tile 0, then R0+R1 of tile 1; wait leaves the
   // tile-1 pair in flight (the steady-state queue).
   stage_a(0, 0);
-  stage_b(0, 0);
+  stage_b(0, 0, c0);
   stage_a(0, 1);
-  stage_b(0, 1);
+  stage_b(0, 1, c0);
   // ordering fence: tile-0 glds must be OLDER than tile-1's so the
   // counted vmcnt below guards exactly the tile-1 pair
   asm volatile("" ::: "memory");
   stage_a(1, 0);
-  stage_b(1, 0);
+  stage_b(1, 0, c1);
   if (BNT == 256) {
     if (DEEP)
       asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -328,7 +404,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_8p(
         bhi[ni][1] = frag<SWZ>(Bb, wc * 4 + 2 + ni, 1, fr, fq);
       }
     }
-    stage_b(t + 1, 1);
+    stage_b(t + 1, 1, c1);
     P8_BAR_MFMA(0, 1, bhi, );
 
     // phase 3: A(mi half 1) reads; stage R0(t+2)
@@ -341,7 +417,11 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_8p(
     P8_BAR_MFMA(1, 0, blo, );
 
     // phase 4: no reads; stage R1(t+2); the tile's single counted wait
-    stage_b(t + 2, 0);
+    stage_b(t + 2, 0, c2);
+    if (TAPB) {  // to the cursors of t+2 and min(t+3, ntiles-1)
+      c1 = c2;
+      if (t + 3 < ntiles) tap_next(c2, ts, ga, N, ldb);
+    }
     if (BNT == 256) {
       if (DEEP)
         asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
@@ -355,9 +435,33 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_8p(
     P8_QUAD(1, 1, bhi);
     if (!(TWEAK & 2)) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_s_barrier();
+    if (TAPR) {
+      // end of a tap: its sum goes through bf16, as the dcol GEMM stored
+      // it, and the taps add up in fp32 in (r, s) order, as col2im added
+      // them: dx / y bit for bit what dcol GEMM + col2im gives
+      tap_k += BK;
+      if (tap_k == ga.C) {
+        tap_k = 0;
+        #pragma unroll
+        for (int i = 0; i < MI; ++i)
+          #pragma unroll
+          for (int j = 0; j < 4; ++j)
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              tot[TAPR ? i : 0][j][r] += bf2f(f2bf(acc[i][j][r] + 0.f));
+              acc[i][j][r] = 0.f;
+            }
+      }
+    }
   }
 #undef P8_BAR_MFMA
 #undef P8_QUAD
+  if (TAPR) {
+    #pragma unroll
+    for (int i = 0; i < MI; ++i)
+      #pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = tot[TAPR ? i : 0][j];
+  }
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -445,6 +549,8 @@ static int p8_enabled() {
       P8_SETATTR((gemm_tn_8p<true, 2, true>), L256);
       P8_SETATTR((gemm_tn_8p<false, 2, false, 128, 2>), L128);
       P8_SETATTR((gemm_tn_8p<true, 2, false, 128, 2>), L128);
+      P8_SETATTR((gemm_tn_8p<true, 2, false, 256, 2, 1>), L256);
+      P8_SETATTR((gemm_tn_8p<true, 2, false, 128, 2, 2>), L128);
       #undef P8_SETATTR
     }
     return on;
@@ -562,6 +668,101 @@ int launch_gemm_tn_8p_tweak(int tweak, const void* A, const void* B, void* C,
   }
   #undef P8_TW
   return (int)grid.x;
+}
+
+// ---- strided dgrad / convT forward as one tap-sliced GEMM per parity class
+// The class GEMM of (qh, qw): M = Nb*Hq*Wq class pixels, N = C8,
+// K = R2*S2*Ko8 over the class's taps, as conv_parity_implicit builds it.
+struct ClassGemm {
+  ConvGather g;
+  int M, K;
+};
+
+static ClassGemm class_gemm(const DgradDirectArgs& a, int stride, int qh,
+                            int qw) {
+  ClassGemm c{};
+  int prh = (qh + a.pad) % stride, prw = (qw + a.pad) % stride;
+  int R2 = (a.R - prh + stride - 1) / stride;
+  int S2 = (a.S - prw + stride - 1) / stride;
+  int Hq = (a.H - qh + stride - 1) / stride;
+  int Wq = (a.W - qw + stride - 1) / stride;
+  if (Hq <= 0 || Wq <= 0 || R2 <= 0 || S2 <= 0) return c;  // M = 0: empty
+  c.g = make_conv_gather(a.Nb, a.Ho, a.Wo, a.Ko8, Hq, Wq, R2, S2, stride,
+                         a.pad, 2);
+  c.g.off_h = (qh + a.pad - prh) / stride;
+  c.g.off_w = (qw + a.pad - prw) / stride;
+  c.g.oH = a.H;
+  c.g.oW = a.W;
+  c.g.oqh = qh;
+  c.g.oqw = qw;
+  c.M = a.Nb * Hq * Wq;
+  c.K = R2 * S2 * a.Ko8;
+  return c;
+}
+
+// Where the 8p core wins: p8_pick_bnt's floors on rows and blocks, per class
+// (H, W even: all four class grids are equal).  GDLJ_DGRAD_CLASSGEMM_MINM
+// (rows, a positive integer; anything else is ignored) replaces both, for
+// tests and microbenches; read per call.  Blocks are counted on the 256-wide
+// tile for both kinds: the 128-wide kind 3 has at least as many.
+static bool class_floors_ok(long rows, int C8) {
+  if (const char* e = getenv("GDLJ_DGRAD_CLASSGEMM_MINM")) {
+    char* end = nullptr;
+    long v = strtol(e, &end, 10);
+    if (end != e && *end == '\0' && v > 0) return rows >= v;
+  }
+  long blocks = (long)ceil_div((int)rows, p8::BM) * ceil_div(C8, 256);
+  return rows >= p8_min_m() && blocks >= 256;
+}
+
+int conv_dgrad_classgemm_eligible(int Nb, int H, int W, int C8, int Ko8,
+                                  long ldw, int R, int S, int stride,
+                                  int pad) {
+  if (Nb <= 0 || !p8_enabled()) return 0;
+  if (stride != 2 || (H & 1) || (W & 1) || H < 2 || W < 2 || pad < 0) return 0;
+  // the class grid measured to win (profiles/dgrad_classgemm_ab.md); larger
+  // grids that no direct kernel takes stay on dcol + col2im
+  if ((H / 2) * (W / 2) > 16) return 0;
+  // 16-byte B chunks and C rows; a K-tile inside one tap; N >= 192 as
+  // p8_pick_bnt asks of the 256-wide tile
+  if (C8 < 192 || C8 % 8 != 0 || Ko8 % p8::BK != 0 || ldw < Ko8 ||
+      ldw % 8 != 0)
+    return 0;
+  if (R < 2 || S < 2 || R > 8 || S > 8) return 0;
+  // the shallowest class has (R/2)*(S/2) taps: >= 4 K-tiles
+  if ((R / 2) * (S / 2) * Ko8 < 4 * p8::BK) return 0;
+  long rows = (long)Nb * (H / 2) * (W / 2);
+  if (rows >= (1L << 30)) return 0;  // FastDiv range of the row decode
+  return class_floors_ok(rows, C8) ? 1 : 0;
+}
+
+void launch_conv_dgrad_classgemm(const DgradDirectArgs& a, int fp32_taps,
+                                 hipStream_t s) {
+  (void)p8_enabled();  // LDS attributes
+  constexpr int L256 = 2 * (p8::OPTA + 256 * p8::BK * 2);
+  constexpr int L128 = 2 * (p8::OPTA + 128 * p8::BK * 2);
+  const int stride = 2;
+  // dgrad: a.act is the producer's code for a fused act backward, which
+  // this kind never runs; only the convT forward has an epilogue
+  const int act = a.bias_fwd != nullptr ? a.act : 0;
+  for (int qh = 0; qh < stride; ++qh) {
+    for (int qw = 0; qw < stride; ++qw) {
+      ClassGemm c = class_gemm(a, stride, qh, qw);
+      if (c.M <= 0) continue;
+      // lda = the full kernel width (the kernel's TAPB note)
+      #define P8_CLS(BT, TB, LB)                                             \
+        hipLaunchKernelGGL((gemm_tn_8p<true, 2, false, BT, 2, TB>),          \
+                           dim3(ceil_div(c.M, p8::BM), ceil_div(a.C8, BT)),  \
+                           dim3(512), LB, s, (const unsigned short*)a.dy,    \
+                           (const unsigned short*)a.Wt,                      \
+                           (unsigned short*)a.dx, a.bias_fwd, c.M, a.C8,     \
+                           c.K, (long)a.S, a.ldw, act, a.slope, c.g,         \
+                           (const unsigned short*)a.zp)
+      if (fp32_taps) P8_CLS(256, 1, L256);
+      else P8_CLS(128, 2, L128);
+      #undef P8_CLS
+    }
+  }
 }
 
 }  // extern "C"

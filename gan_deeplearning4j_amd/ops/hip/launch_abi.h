@@ -97,7 +97,10 @@ inline ConvGather make_conv_gather(int N, int H, int W, int C, int Ho, int Wo,
 // ------------------------------------------- direct dgrad plan / arguments
 // Which direct strided dgrad kernel takes a geometry, and its tiling.
 struct DgradDirectPlan {
-  int kind;       // 0 ineligible, 1 one-shot kernel, 2 persistent kernels
+  int kind;       // 0 ineligible, 1 one-shot kernel, 2 persistent kernels,
+                  // 3 one gathered 8-phase GEMM per parity class (gemm8p.hip)
+                  // with the taps rounded as dcol stores them, 4 the same
+                  // with all taps accumulated in fp32
   int bm;         // class pixels per tile: 128 or 64 (wide: always 128)
   int qsplit;     // persistent only: 1 = tiles split by row parity
   int lds_bytes;  // dynamic LDS per block
@@ -107,6 +110,8 @@ struct DgradDirectPlan {
 // allow mask of conv_dgrad_direct_plan (wide needs persist as well)
 constexpr int kDgradAllowPersist = 1;
 constexpr int kDgradAllowWide = 2;
+constexpr int kDgradAllowClassGemm = 4;  // kind 3 / 4, the last resort
+constexpr int kDgradClassFp32 = 8;       // kind 4 instead of kind 3
 
 // Arguments of the direct dgrad launch, named for the conv data-grad.  The
 // strided convT FORWARD runs the same kernel with the roles swapped: dy is
@@ -156,6 +161,19 @@ int launch_gemm_tn_8p(const void* A, const void* B, void* C,
 int launch_gemm_tn_8p_tweak(int tweak, const void* A, const void* B, void* C,
                             int M, int N, int K, long lda, long ldb,
                             hipStream_t s);
+// Strided dgrad / convT forward as one gathered GEMM per parity class, B read
+// in place from the [(r,s,c)][ko] pack (a.Wt).  _eligible: geometry, the 8p
+// floors on rows and blocks per class (GDLJ_DGRAD_CLASSGEMM_MINM replaces
+// them, read per call); Nb <= 0 is never eligible.  The launch uses a.bias_fwd
+// / a.act as the epilogue (dgrad: bias_fwd null, identity) and ignores a.y0,
+// a.part and a.stats_part.  fp32_taps = 0: 128-wide tile, every tap's sum
+// rounded to bf16 before the taps add up, dx / y bit-equal to dcol GEMM +
+// col2im; 1: 256-wide tile, one fp32 accumulation over all taps.
+int conv_dgrad_classgemm_eligible(int Nb, int H, int W, int C8, int Ko8,
+                                  long ldw, int R, int S, int stride,
+                                  int pad);
+void launch_conv_dgrad_classgemm(const DgradDirectArgs& a, int fp32_taps,
+                                 hipStream_t s);
 
 // gemm8p_nt.hip -- arguments as launch_gemm_nt; returns 1 and launches when
 // the shape is eligible (GDLJ_NT8P, GDLJ_NT8P_MINK), else 0.
@@ -196,11 +214,14 @@ int launch_conv_direct_smallc(const void* img, const void* Wp, void* C,
                               int act, float slope, hipStream_t s);
 
 // conv_dgrad_direct.hip
-// Allow mask from GDLJ_DGRAD_PERSIST / GDLJ_DGRAD_WIDE, read per call.
+// Allow mask from GDLJ_DGRAD_PERSIST / GDLJ_DGRAD_WIDE /
+// GDLJ_DGRAD_CLASSGEMM / GDLJ_DGRAD_CLASSGEMM_FP32, read per call.
 int conv_dgrad_direct_allow();
 // Tries the wide, then the persistent kernel (as `allow` permits), then the
-// one-shot one.
-DgradDirectPlan conv_dgrad_direct_plan(int H, int W, int C8, int Ko8,
+// one-shot one, and where all three refuse the class GEMMs (kind 3, or 4
+// with kDgradClassFp32), whose floors depend on the batch Nb (0 = unknown:
+// never).
+DgradDirectPlan conv_dgrad_direct_plan(int Nb, int H, int W, int C8, int Ko8,
                                        long ldw, int R, int S, int stride,
                                        int pad, int allow);
 void launch_conv_dgrad_direct(const DgradDirectArgs& a, DgradDirectPlan plan,

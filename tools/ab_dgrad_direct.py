@@ -110,17 +110,21 @@ def bench_pact(nb, cin, h, cout, r, stride, pad, want_bias=True):
     return dt, x.grad.float().abs().sum().item()
 
 
-def bench_convt(nb, cin, hi, cout, r, stride, pad):
+def bench_convt(nb, cin, hi, cout, r, stride, pad, act="identity",
+                with_bias=False):
     g = torch.Generator().manual_seed(5)
     x = (torch.randn(nb, cin, hi, hi, generator=g) * 0.5).to(
         "cuda", torch.bfloat16)
     w = (torch.randn(cin, cout, r, r, generator=g) * 0.1).to(
         "cuda", torch.bfloat16)
+    b = None
+    if with_bias:
+        b = (torch.randn(cout, generator=g) * 0.1).to("cuda", torch.bfloat16)
     out = []
 
     def step():
-        out[:] = [gpu_ops.conv_transpose2d(x, w, None, stride, pad,
-                                           "identity", emit_stats=True)]
+        out[:] = [gpu_ops.conv_transpose2d(x, w, b, stride, pad, act,
+                                           emit_stats=True)]
         gpu_ops.take_bn_stats(out[0])
 
     with torch.no_grad():
@@ -195,7 +199,123 @@ def report(name, fn, geom=None):
               f"{'-' if ws is None else '%.2f GB' % (ws / 1e9)}", flush=True)
 
 
+# ---------------------------------------------------------------------------
+# The 4x4 class grid (conv4 dgrad / convT1 forward of DCGAN-64, conv5 dgrad /
+# convT1 forward of DCGAN-128): no direct kernel takes it.  Two modes:
+#   step0     arm A = gemm_tn + col2im(_stats), arm B = conv_parity_implicit
+#             on class packs built once, both through the raw extension
+#             entry points (the go / no-go measurement, runs on any build);
+#   classgemm arm A = GDLJ_DGRAD_CLASSGEMM=0 (dcol + col2im), arm B = default
+#             (the class GEMMs behind the direct bindings, dcol's roundings),
+#             arm C = GDLJ_DGRAD_CLASSGEMM_FP32=1 (one fp32 accumulation on
+#             the 256-wide tile), through gpu_ops.  The convT rows ask for BN
+#             statistics, which only arm C serves on this route.
+# Arm A is timed three times; B wins if it beats the fastest A by more than
+# A's spread.
+CLASS4_SHAPES = [
+    # name, Nb, H (= W, full-res side), C8, Ko8, R, pad   [dgrad naming]
+    ("dcgan64_conv4_b16384", 16384, 8, 256, 512, 4, 1),
+    ("dcgan128_conv5_b2048", 2048, 8, 512, 512, 4, 1),
+]
+
+
+def class4_data(nb, h, c8, ko8, r, pad):
+    g = torch.Generator().manual_seed(6)
+    hc = (h + 2 * pad - r) // 2 + 1
+    dy = (torch.randn(nb, hc, hc, ko8, generator=g) * 0.5).to(
+        "cuda", torch.bfloat16)
+    wc = (torch.randn(c8, r, r, ko8, generator=g) * 0.05).to(
+        "cuda", torch.bfloat16)                       # [c][R][S][ko]
+    wt = wc.permute(1, 2, 0, 3).reshape(r * r * c8, ko8).contiguous()
+    bias = (torch.randn(c8, generator=g) * 0.1).to("cuda")
+    return hc, dy, wc, wt, bias
+
+
+def step0_row(name, nb, h, c8, ko8, r, pad, convt):
+    ext = gpu_ops.hip_ext()
+    hc, dy, wc, wt, bias = class4_data(nb, h, c8, ko8, r, pad)
+    zp = gpu_ops._zero_page(dy.device)
+    packs = gpu_ops._parity_class_packs(wc, 2, pad)
+    dy2d = dy.view(-1, ko8)
+    gamma, beta = torch.ones_like(bias), torch.zeros_like(bias)
+    none = torch.empty(0, device="cuda")
+    out = []
+
+    def arm_a():
+        dcol = ext.gemm_tn(dy2d, wt, None, 0, 0.0, False)
+        if convt:
+            y, ssum, ssq = ext.col2im_stats(dcol, nb, h, h, c8, hc, hc, r, r,
+                                            2, pad, r * r * c8, bias, 3, 0.2)
+            ext.bn_fwd_train_pre(y, ssum, ssq, gamma, beta, none, none, 0.1,
+                                 1e-5)
+        else:
+            y = ext.col2im(dcol, nb, h, h, c8, hc, hc, r, r, 2, pad,
+                           r * r * c8, None, 0, 0.0)
+        out[:] = [y]
+
+    def arm_b():
+        y = ext.conv_parity_implicit(dy, packs, bias if convt else None, zp,
+                                     nb, hc, hc, ko8, h, h, c8, r, r, 2, pad,
+                                     3 if convt else 0, 0.2)
+        if convt:  # separate statistics pass, as the binding would run it
+            ext.bn_fwd_train(y.view(nb, h, h, c8), gamma, beta, none, none,
+                             0.1, 1e-5)
+        out[:] = [y]
+
+    res = []
+    with torch.no_grad():
+        for arm, fn in (("dcol", arm_a), ("dcol", arm_a), ("dcol", arm_a),
+                        ("parity", arm_b)):
+            res.append((arm, timed(fn), out[0].float().abs().sum().item()))
+    print_verdict(name + ("_convT" if convt else "_dgrad"), res, "dcol",
+                  "parity")
+
+
+def classgemm_row(name, nb, h, c8, ko8, r, pad, convt):
+    hc = (h + 2 * pad - r) // 2 + 1
+    off = {"GDLJ_DGRAD_CLASSGEMM": "0"}
+    on = {"GDLJ_DGRAD_CLASSGEMM": "1"}
+    if convt:
+        fn = lambda: bench_convt(nb, ko8, hc, c8, r, 2, pad,  # noqa: E731
+                                 "lrelu", True)
+    else:
+        fn = lambda: bench_one(nb, c8, h, ko8, r, 2, pad)  # noqa: E731
+    fp32 = dict(on, GDLJ_DGRAD_CLASSGEMM_FP32="1")
+    res = [(arm, *with_env(env, fn)) for arm, env in (
+        ("dcol", off), ("dcol", off), ("dcol", off), ("classgemm", on),
+        ("classgemm_fp32", fp32))]
+    for arm in ("classgemm", "classgemm_fp32"):
+        print_verdict(name + ("_convT" if convt else "_dgrad+wgrad"),
+                      [x for x in res if x[0] in ("dcol", arm)], "dcol", arm)
+
+
+def print_verdict(name, res, a_name, b_name):
+    at = [t for arm, t, _ in res if arm == a_name]
+    bt = [t for arm, t, _ in res if arm == b_name][0]
+    c0 = res[0][2]
+    ok = all(abs(c - c0) < 1e-3 * abs(c0) for _, _, c in res)
+    match = "match" if ok else "MISMATCH " + " vs ".join(
+        f"{c}" for _, _, c in res)
+    win = "WINS" if min(at) - bt > max(at) - min(at) else "no win"
+    print(f"{name}: {a_name} " + " / ".join(f"{t:.3f}" for t in at) +
+          f" ms (spread {max(at) - min(at):.3f}) | {b_name} {bt:.3f} ms | "
+          f"{b_name} - fastest {a_name} {bt - min(at):+.3f} ms: "
+          f"{b_name.upper()} {win} [{match}]", flush=True)
+
+
 if __name__ == "__main__":
+    mode = sys.argv[1] if len(sys.argv) > 1 else ""
+    if mode in ("step0", "classgemm"):
+        row = step0_row if mode == "step0" else classgemm_row
+        for name, *geom in CLASS4_SHAPES:
+            row(name, *geom, convt=False)
+            row(name, *geom, convt=True)
+        if mode == "classgemm":  # unchanged controls
+            report("conv2_r4_b16384 (control)",
+                   lambda: bench_one(*SHAPES[0][1:]))
+            report("conv3_r4_b16384 (control)",
+                   lambda: bench_one(*SHAPES[1][1:]))
+        sys.exit(0)
     # geom = (Nb, H, C8, Ko8, R, pad) in the kernel's dgrad naming
     for name, *args in SHAPES:
         nb, cin, h, cout, r, _, pad = args
